@@ -14,6 +14,13 @@ frames with no other collective: per-GPU work is fixed ("weak" scaling) and
 
 Inputs are synthetic and seeded (dreammesh4d_amd/synthetic.py), resident in HBM before the
 timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--full` also measures what
+is reported beside the headline: the same step with a depth gradient and with the full backward, the
+8-view step, the dynamic- and static-stage iterations/sec and the CPU baseline.  `--dump-outputs DIR`
+writes what the last timed step computed (rank 0) as DIR/<name>.npy: the step's outputs and the
+deformation network's parameter gradients, float32; arrays above DUMP_WHOLE elements as a fixed,
+seeded sample of DUMP_SAMPLE elements.
 """
 import argparse
 import json
@@ -50,14 +57,54 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)      # ~0.45 s timed: 50 steps sit inside the clock / power fluctuation of a box (+-4 %)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-iters", action="store_true", help="skip the dynamic-stage iterations/sec measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the headline: the with-depth-gradient / full-backward legs, the 8-view "
+                         "step, the dynamic- and static-stage iterations/sec and the CPU baseline (off: the headline step alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (images, radii, skinned vertices, parameter gradients) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-iters", action="store_true", help="with --full: skip the dynamic- / static-stage iterations/sec measurements")
     ap.add_argument("--cpu-baseline-views", type=int, default=24)     # ~12 s of host work at ~2 views/s
     ap.add_argument("--views-per-frame", type=int, default=VIEWS_PER_FRAME,
                     help="views per frame of the headline step (default 5 = configs[3]'s 4 SDS + 1 ref; the per-kernel scaling tables use 1/2/4/5)")
-    ap.add_argument("--no-step8", action="store_true", help="skip the 8-view step (the shipped YAML's iteration) timed beside the headline")
-    ap.add_argument("--no-variants", action="store_true", help="skip the with-depth-gradient / full-backward legs")
-    return ap.parse_args()
+    ap.add_argument("--no-step8", action="store_true", help="with --full: skip the 8-view step (the shipped YAML's iteration) timed beside the headline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the with-depth-gradient / full-backward legs")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_WHOLE = 1 << 20       # --dump-outputs: arrays of up to this many elements are written whole,
+DUMP_SAMPLE = 1 << 19      # larger ones as this many elements at fixed positions (seeded by the array's name, sorted flat indices)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(wl, out):
+    """What a caller of the timed step receives, as host arrays keyed by name: the step's outputs (images, radii, skinned
+    vertices) and the deformation network's parameter gradients after the exchange.  Large arrays are sampled (DUMP_SAMPLE)."""
+    import zlib
+
+    named = [(k, v) for k, v in out.items() if torch.is_tensor(v)]
+    named += [("grad." + k, p.grad) for k, p in wl.net.named_parameters() if p.grad is not None]
+    arrays = {}
+    for name, t in named:
+        x = t.detach().reshape(-1)
+        if x.numel() > DUMP_WHOLE:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(x.numel(), DUMP_SAMPLE, replace=False))
+            x = x[torch.from_numpy(idx).to(x.device)]
+        a = x.cpu().numpy()
+        arrays[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    return arrays
+
+
+def dump_outputs(arrays, directory):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs exceed the {DUMP_MAX_BYTES}-byte bound")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 class Workload:
@@ -225,10 +272,11 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(dev)
 
-    def timed_leg(wl, steps, warmup, settle, variants):
+    def timed_leg(wl, steps, warmup, settle, variants, keep_outputs=False):
         """One timed region of `steps` steps of `wl` (+ the exchange), after `warmup` + `settle` untimed steps; with `variants` also
         the same step with a gradient on the depth image and with the static appearance learnable (the other two instantiations
-        of the blend backward).  Returns the numbers of the leg; `elapsed` is the MAX over ranks."""
+        of the blend backward).  Returns the numbers of the leg; `elapsed` is the MAX over ranks.  `keep_outputs`: the leg also
+        holds what the last timed step computed (step_outputs), copied to the host before anything else runs."""
         import ctypes
         wl.step()                                          # builds the HexPlane gather plan of the (static) node set
         # 35.76 M parameters, but the spatial grids only receive gradient at the texels the static nodes touch (the
@@ -236,21 +284,23 @@ def main():
         reducer = GradAllReducer(wl.net.parameters(), touched=touched_from_plan(wl.net.deformation_net.grid, wl.net._hex_plan))
 
         def step():
-            wl.step()
+            out = wl.step()
             reducer()       # the one exchange step of the path: data-parallel gradient all-reduce (no-op for 1 GPU)
+            return out
 
         def region(n):
             L.dm4d_profile_enable(1 << K_RENDER_BWD)
             t0 = time.perf_counter()
-            for _ in range(n):
+            for _ in range(n - 1):
                 step()
+            out = step()
             sync()
             el = time.perf_counter() - t0
             L.dm4d_profile_enable(0)
             tot = ctypes.c_double(0.0)
             nl = L.dm4d_profile_collect(K_RENDER_BWD, ctypes.byref(tot))
             # seconds of the dominant kernel per STEP (a step's views may go through several launches of it: the pipelined backward)
-            return el, tot.value / n * 1e-3, int(nl)
+            return el, tot.value / n * 1e-3, int(nl), out
 
         for _ in range(warmup):
             step()
@@ -261,21 +311,23 @@ def main():
             step()
         sync()
         D_views = wl.renderer.check()      # also validates the duplicate-list capacity
-        elapsed, avg_s, n_launch = region(steps)
+        elapsed, avg_s, n_launch, last = region(steps)
         wl.renderer.check()
+        outputs = step_outputs(wl, last) if keep_outputs else None
+        del last
         if world > 1:
             t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         leg = {"elapsed": elapsed, "steps": steps, "avg_s": avg_s, "n_launch": n_launch, "D_mean": float(np.mean(D_views)),
-               "reducer": reducer, "with_depth": None, "full": None}
+               "reducer": reducer, "with_depth": None, "full": None, "outputs": outputs}
         if variants and world == 1 and not wl.depth_grad:      # the same step with a gradient on the depth image (48-byte records)
             wl.depth_grad = True
             for _ in range(5):
                 step()
             sync()
             n_wd = min(steps, 100)
-            el, av, nl = region(n_wd)
+            el, av, nl, _ = region(n_wd)
             leg["with_depth"] = (el / n_wd, av, nl)
             # ... and with the static appearance learnable: the FULL (non-lean) blend backward
             wl.set_static_learnable(True)
@@ -283,7 +335,7 @@ def main():
                 step()
             sync()
             n_full = min(steps, 20)
-            el, av, nl = region(n_full)
+            el, av, nl, _ = region(n_full)
             leg["full"] = (el / n_full, av, nl)
             wl.set_static_learnable(False)
             wl.depth_grad = False
@@ -342,12 +394,15 @@ def main():
     vpf = int(args.views_per_frame)
     wl = Workload(dev, rank, world, views_per_frame=vpf)
     settle = 400 if vpf <= 2 else 200       # ~0.4-0.8 s of untimed GPU work either way
-    leg = timed_leg(wl, args.steps, args.warmup, settle, variants=not args.no_variants)
+    dump = args.dump_outputs is not None and rank == 0
+    leg = timed_leg(wl, args.steps, args.warmup, settle, variants=args.full and not args.no_variants, keep_outputs=dump)
+    if dump:
+        dump_outputs(leg["outputs"], args.dump_outputs)
     reducer = leg["reducer"]
     head = leg_numbers(wl, leg)
     # the shipped YAML's iteration (8 views per step: what rounds 1-5 reported as `value`), on the same scene and the same box
     step8 = None
-    if world == 1 and not args.no_step8 and vpf != VIEWS_PER_FRAME_YAML:
+    if args.full and world == 1 and not args.no_step8 and vpf != VIEWS_PER_FRAME_YAML:
         wl8 = Workload(dev, rank, world, views_per_frame=VIEWS_PER_FRAME_YAML, sc=wl.sc)
         leg8 = timed_leg(wl8, args.steps, args.warmup, 400, variants=not args.no_variants)
         step8 = leg_numbers(wl8, leg8)
@@ -369,7 +424,7 @@ def main():
                                    f"512x512; per view: skinning + face->Gaussian + RGB pass + normal pass, fwd+bwd"
                                    + ("" if wl.depth_grad else "; no gradient on the depth image, as in the shipped configuration (no depth loss)"),
                        "comparability": "rounds 1-5 reported the 8-unit step (4 frames x 2 views: the shipped YAML's iteration) as `value`: it is `step_8_views` "
-                                        "below, timed in this same run; from round 6 on `value` is the 20-unit step BASELINE configs[3] names.  Rounds 1-2 timed "
+                                        "(timed in the same run with --full); from round 6 on `value` is the 20-unit step BASELINE configs[3] names.  Rounds 1-2 timed "
                                         "WITH a gradient on the depth image (48-byte records): they compare with `step_8_views.with_depth_gradient`",
                        "views_per_step_per_gpu": wl.views_per_step, "untimed_settle_steps": settle, "frames_per_step_per_gpu": FRAMES_PER_STEP,
                        "views_per_frame": vpf,
@@ -384,7 +439,7 @@ def main():
                 out[k] = head[k]
         if step8 is not None:
             out["step_8_views"] = step8
-        if world == 1 and not args.no_iters:
+        if args.full and world == 1 and not args.no_iters:
             # BASELINE.json's second metric, reported beside the headline one (never used for `value`)
             try:
                 out["config"].update(dynamic_stage_iterations(wl, dev))
@@ -398,13 +453,13 @@ def main():
             except Exception as e:
                 out["config"]["dynamic_stage_20_units_iters_per_sec"] = None
                 out["config"]["dynamic_stage_20_units_error"] = repr(e)[:200]
-        if world == 1 and not args.no_iters:
+        if args.full and world == 1 and not args.no_iters:
             try:
                 out["config"].update(static_stage_iterations(dev))
             except Exception as e:
                 out["config"]["static_stage_iters_per_sec"] = None
                 out["config"]["static_stage_error"] = repr(e)[:200]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl, args.cpu_baseline_views)
         print(json.dumps(out))
     if world > 1:

@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 R=$1; shift
 for r in $(seq 1 $R); do
   for v in "$@"; do
-    echo "== [$v] round $r: $(env $v python $REPO/bench.py --no-cpu-baseline --no-iters $BENCH_ARGS 2>/dev/null | tail -1 | python -c '
+    echo "== [$v] round $r: $(env $v python $REPO/bench.py --full --no-cpu-baseline --no-iters $BENCH_ARGS 2>/dev/null | tail -1 | python -c '
 import sys,json
 d=json.loads(sys.stdin.read())
 s=d.get("step_8_views") or {}

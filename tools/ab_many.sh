@@ -7,7 +7,7 @@ cp $REPO/dreammesh4d_amd/libdm4d_hip.so /tmp/libdm4d_keep.so
 for r in $(seq 1 $R); do
   for v in "$@"; do
     cp $REPO/$v $REPO/dreammesh4d_amd/libdm4d_hip.so
-    echo "== $v round $r: $(python $REPO/bench.py --no-cpu-baseline --no-iters $BENCH_ARGS 2>/dev/null | tail -1 | python -c '
+    echo "== $v round $r: $(python $REPO/bench.py --full --no-cpu-baseline --no-iters $BENCH_ARGS 2>/dev/null | tail -1 | python -c '
 import sys,json
 d=json.loads(sys.stdin.read())
 s=d.get("step_8_views") or {}

@@ -5,6 +5,6 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 R=$1; shift
 for r in $(seq 1 $R); do
   for t in "$@"; do
-    echo "== [$t] round $r: $(python $REPO/$t/bench.py --no-cpu-baseline --no-iters --steps 400 2>/dev/null | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], "ms/step", d["value"], "views/s, bwd", d["roofline"]["avg_launch_us"], "us; with depth", d["with_depth_gradient"]["ms_per_step"], "full", d["roofline_full"]["ms_per_step"])')"
+    echo "== [$t] round $r: $(python $REPO/$t/bench.py --full --no-cpu-baseline --no-iters --steps 400 2>/dev/null | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], "ms/step", d["value"], "views/s, bwd", d["roofline"]["avg_launch_us"], "us; with depth", d["with_depth_gradient"]["ms_per_step"], "full", d["roofline_full"]["ms_per_step"])')"
   done
 done

@@ -24,7 +24,7 @@ readme = ["# profiles/\n\nrocprofv3 summaries of `bench.py` on one MI355X (gfx95
           f"`tools/refresh_profiles_r06.sh {tag}` ran on the GPU box.  Round 6: the headline step is BASELINE configs[3]'s per-GPU share, 4 frames x "
           "(4 SDS views + 1 reference view) = 20 (frame, view) units; the 8-unit step of rounds 1-5 (the shipped YAML's iteration) is profiled beside it.  The "
           "kernel names are the same at both shapes, so each shape has its own rocprofv3 runs (`bench.py --views-per-frame 5 | 2 --no-step8 --no-variants`).\n\n"
-          f"* `r06_bench.json` -- the JSON line of `python bench.py` (un-profiled, with `step_8_views` and `cpu_baseline`): {bench['value']} {bench['unit']}, "
+          f"* `r06_bench.json` -- the JSON line of `python bench.py --full` (un-profiled, with `step_8_views` and `cpu_baseline`): {bench['value']} {bench['unit']}, "
           f"{bench['ms_per_step']} ms per 20-unit step, whole-view fraction {bench['config']['whole_view_frac_of_hbm_roofline']}, roofline.frac {bench['roofline']['frac']}; "
           f"8-unit step {bench['step_8_views']['value']} views/s, {bench['step_8_views']['ms_per_step']} ms, whole-view fraction {bench['step_8_views']['whole_view_frac_of_hbm_roofline']}\n"]
 for vpf, name in ((5, "20v"), (2, "8v")):

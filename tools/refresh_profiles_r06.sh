@@ -8,7 +8,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $REPO/bench.py > $OUT/bench.json 2> $OUT/bench.err
+python $REPO/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 for V in 5 2; do
   A="--views-per-frame $V --no-step8 --no-variants --no-cpu-baseline --no-iters"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_v$V -o bench -- python $REPO/bench.py $A --steps 50 --warmup 10 > $OUT/stats_v$V.log 2>&1
