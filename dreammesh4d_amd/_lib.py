@@ -239,6 +239,12 @@ _SIGNATURES = {
     "dm4d_step_backward": (C.c_int, [vp] * 7),
     "dm4d_step_backward_rgb": (C.c_int, [vp] * 6),
     "dm4d_step_views": (vp, [vp]),
+    "dm4d_tex_atlas_size": (C.c_int32, [C.c_int32, C.c_int32]),
+    "dm4d_tex_atlas_init": (C.c_int, [C.c_int32] * 3 + [vp] * 8),
+    "dm4d_mesh_raster_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "dm4d_mesh_raster": (C.c_int, [C.c_int32] * 4 + [vp] * 6 + [C.c_int32, vp, C.c_size_t, vp, vp, vp, vp]),
+    "dm4d_tex_claim_bytes": (C.c_size_t, [C.c_int32]),
+    "dm4d_tex_accumulate": (C.c_int, [C.c_int32, vp, vp, C.c_int64, C.c_uint32, vp, C.c_size_t, C.c_int32, vp, vp, vp]),
 }
 
 

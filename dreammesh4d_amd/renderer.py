@@ -142,7 +142,8 @@ class DiffGaussianTemporal:
     """The reference's ``diff-sugar-rasterizer-temporal`` renderer over a ``sugar.DynamicSuGaR`` geometry.
 
     ``batch_forward(batch)`` takes the reference's batch dict (``c2w [B,4,4]``, ``fovy [B]`` radians, ``height``,
-    ``width``, ``rays_o`` / ``rays_d [B,H,W,3]``, ``timestamp [B]`` and/or ``frame_indices [B]``) and returns the
+    ``width``, ``rays_o`` / ``rays_d [B,H,W,3]``, ``timestamp [B]`` and/or ``frame_indices [B]``; with neither, the canonical
+    Gaussians are rendered, ``render_canonical``) and returns the
     reference's output dict: ``comp_rgb``, ``comp_normal``, ``comp_normal_from_dist`` [B,H,W,3], ``comp_depth``,
     ``comp_mask`` [B,H,W,1], and the per-view lists ``viewspace_points`` (their ``.grad`` receives the screen-space
     mean gradients), ``visibility_filter``, ``radii``."""
@@ -180,7 +181,7 @@ class DiffGaussianTemporal:
         ts = batch.get("timestamp")
         fi = batch.get("frame_indices")
         if ts is None and fi is None:
-            raise NotImplementedError("the static stage goes through dreammesh4d_amd.diff_gaussian_rasterization")
+            return self._canonical_batch(w2c, full, bg, H, W, math.tan(0.5 * fov0))
         # node outputs once per distinct (timestamp, frame) of the batch (dynamic_sugar.py:367-405 caches them)
         dx, dr, ds, do, frame_index = g.timed_node_outputs(ts, fi)
         r = self._renderer(H, W, math.tan(0.5 * fov0))
@@ -201,6 +202,32 @@ class DiffGaussianTemporal:
 
     __call__ = batch_forward
 
+    def render_canonical(self, w2c, full, bg, H, W, tanfov, means2D=None):
+        """The canonical (static) Gaussians from B cameras: the reference's branch for a camera with neither ``timestamp`` nor
+        ``frame_idx`` (…temporal.py:149-157) -- ``get_xyz``, ``get_scaling``, ``get_rotation``, ``get_opacity`` and ``shs =
+        get_features`` (degree 0: max(SH2RGB(dc), 0), ``texture_export.canonical_gaussians``), one ``gviews.render_gaussian_views`` call."""
+        from . import gviews
+        from .texture_export import canonical_gaussians
+
+        g = self.geometry
+        key = ("canonical", int(H), int(W), round(float(tanfov), 9))
+        if key not in self._renderers:
+            self._renderers[key] = gviews.GaussianViews(g.n_gaussians, H, W, tanfov, g.device)
+        m, q, s, o, c6 = canonical_gaussians(g)
+        return gviews.render_gaussian_views(self._renderers[key], m, q, s, o, c6, w2c, full, torch.cat([bg, bg]), means2D=means2D)
+
+    def _canonical_batch(self, w2c, full, bg, H, W, tanfov) -> Dict:
+        """batch_forward of a batch without timestamps: no normal pass, no normal-from-depth (the reference's `static` branch)."""
+        g = self.geometry
+        B = int(w2c.shape[0])
+        vsp = [torch.zeros(g.n_gaussians, 3, device=g.device, requires_grad=True) for _ in range(B)]
+        out = self.render_canonical(w2c, full, bg, H, W, tanfov, means2D=torch.stack(vsp))
+        depth = _where_detached(out["depth"], out["alpha"] > 0.99)
+        return {"comp_rgb": out["color"][:, :3].clamp(0, 1).permute(0, 2, 3, 1), "comp_depth": depth.permute(0, 2, 3, 1),
+                "comp_mask": out["alpha"].permute(0, 2, 3, 1), "comp_normal": None, "comp_normal_from_dist": None,
+                "viewspace_points": vsp, "visibility_filter": [out["radii"][b] > 0 for b in range(B)],
+                "radii": [out["radii"][b] for b in range(B)]}
+
     def forward(self, viewpoint_camera: Camera, bg_color=None, scaling_modifier=1.0, override_color=None,
                 compute_normal_from_dist=True, **kwargs) -> Dict:
         """Single view in the reference's signature (the matrices of `viewpoint_camera` are used as given)."""
@@ -211,6 +238,14 @@ class DiffGaussianTemporal:
         bg = self.background_tensor if bg_color is None else bg_color.to(g.device)
         if not self.training:
             bg = 1.0 - bg
+        if viewpoint_camera.timestamp is None and viewpoint_camera.frame_idx is None:
+            vsp = torch.zeros(g.n_gaussians, 3, device=g.device, requires_grad=True)
+            out = self.render_canonical(viewpoint_camera.world_view_transform[None], viewpoint_camera.full_proj_transform[None], bg, H, W,
+                                        math.tan(0.5 * float(viewpoint_camera.FoVy)), means2D=vsp[None])
+            depth = _where_detached(out["depth"][0], out["alpha"][0] > 0.99)
+            return {"render": out["color"][0, :3].clamp(0, 1), "normal": None, "normal_from_dist": None, "depth": depth,
+                    "mask": out["alpha"][0], "viewspace_points": vsp, "visibility_filter": out["radii"][0] > 0,
+                    "radii": out["radii"][0], "raw_normal": None, "raw_normal_from_dist": None}
         ts = None if viewpoint_camera.timestamp is None else viewpoint_camera.timestamp.reshape(1)
         fi = None if viewpoint_camera.frame_idx is None else viewpoint_camera.frame_idx.reshape(1)
         dx, dr, ds, do, frame_index = g.timed_node_outputs(ts, fi)

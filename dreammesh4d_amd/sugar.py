@@ -355,7 +355,7 @@ class SuGaR(nn.Module):
     ``_sh_coordinates_dc`` / ``_rest``), so its checkpoints load by name (wire_formats.load_geometry).  Unlike the
     dynamic stage every property is differentiable here: they are the torch ops of geometry.py evaluated per call
     (positions, scales, opacities, colours are LEARNT in this stage, sugar.py:329-382), and they feed the HIP
-    rasterizer through the drop-in operator.  The mesh-extraction / texture-baking half of SuGaRModel is out of scope."""
+    rasterizer through the drop-in operator.  Texture baking and the textured export: ``texture_export`` (mesh extraction / postprocessing stay out of scope)."""
 
     def __init__(self, verts, faces, n_gaussians_per_surface_triangle=6, spatial_extent=3.8, vertex_colors=None,
                  learn_positions=True, learn_opacities=True, learn_scales=True, freeze_gaussians=False,

@@ -738,11 +738,22 @@ class SingleImageDataModule(TemporalImageDataModule):
                          None if mask is None else mask.reshape(1, *mask.shape[-3:]))
 
 
+@dataclass
+class _BaseSuGaRSystemConfig:                         # BaseSuGaRSystem.Config (C/system/base.py:38-44): the export's keys
+    postprocess: bool = False
+    postprocess_density_threshold: float = 0.1
+    postprocess_iterations: int = 5
+    square_size_in_texture: int = 20
+    export_resolution: int = 1024
+
+
 class _SystemBase:
     """BaseLift3DSystem.configure (threestudio/systems/base.py:262-282): the plugins of a `system:` block by name."""
 
     def _plugins(self, cfg, guidance_key, model):
         self.cfg = cfg
+        names = {f.name for f in dataclasses.fields(_BaseSuGaRSystemConfig)}
+        self.export_cfg = parse_structured(_BaseSuGaRSystemConfig, {k: v for k, v in dict(cfg).items() if k in names})
         self.geometry = find(cfg["geometry_type"])(cfg["geometry"])
         self.material = find(cfg["material_type"])(cfg.get("material"))
         self.background = find(cfg["background_type"])(cfg.get("background"))
@@ -755,6 +766,25 @@ class _SystemBase:
         for m in (self.geometry, self.renderer, self.guidance):
             if m is not None and hasattr(m, "do_update_step"):
                 m.do_update_step(epoch, global_step)
+
+    def _predict_fovy_deg(self, data):
+        rc = dict(getattr(data.cfg, "random_camera", None) or {})
+        return float(rc.get("eval_fovy_deg", data.cfg.default_fovy_deg))      # the shipped yaml: ${data.default_fovy_deg}
+
+    def bake_texture(self, n_views=None, seed=0, chunk=8):
+        """``on_predict_start`` + the predict epoch (C/system/base.py:72-292): the atlas of `square_size_in_texture`, the 120 predict
+        views at `export_resolution` (``texture_export.predict_cameras``, seeded), the canonical Gaussians baked into it.
+        Returns (atlas, texture [T,T,3])."""
+        from . import texture_export as tx
+
+        c = self.export_cfg
+        if c.postprocess:
+            raise NotImplementedError("postprocess: true (postprocess_mesh, C/system/base.py:326ff: density-based removal of border "
+                                      "triangles) is not mirrored; the shipped configurations do not set it")
+        atlas = tx.build_atlas(self.geometry, int(c.square_size_in_texture))
+        cams = tx.predict_cameras(tx.N_PREDICT_VIEWS if n_views is None else int(n_views), int(c.export_resolution), int(c.export_resolution),
+                                  seed=seed, fovy_deg=self._export_fovy_deg)
+        return atlas, tx.bake_texture(self.geometry, atlas, cams, chunk=chunk).texture()
 
 
 @register("sugar-4dgen-system")
@@ -770,6 +800,7 @@ class SuGaR4DGen(_SystemBase):
         from .dynamic_stage import DynamicStage
 
         self._plugins(cfg, "guidance_zero123", model)
+        self._export_fovy_deg = self._predict_fovy_deg(data)
         g = self.geometry
         dev = g.device
         H, W = int(data.height), int(data.width)
@@ -792,6 +823,15 @@ class SuGaR4DGen(_SystemBase):
         self.do_update_step(0, self.stage.global_step)
         return self.stage.iteration()
 
+    def export(self, out_dir, n_views=None, seed=0, chunk=8, video_length=32):
+        """``--export`` (reference README.md:91-93; C/system/sugar_4dgen.py:594-640): the texture baked from the canonical Gaussians,
+        then ``<out_dir>/extracted_textured_meshes/extracted_mesh_{i}.obj`` (+ .mtl, .png) of the deformed mesh at the 32 timestamps
+        linspace(0, 1, 34)[1:-1].  Returns the OBJ paths."""
+        from . import texture_export as tx
+
+        atlas, texture = self.bake_texture(n_views, seed, chunk)
+        return tx.export_textured_sequence(out_dir, self.geometry, texture, tx.predict_timestamps(video_length), atlas)
+
 
 @register("sugar-static-system")
 class SuGaRStatic(_SystemBase):
@@ -803,6 +843,7 @@ class SuGaRStatic(_SystemBase):
         from .static_stage import StaticStage
 
         self._plugins(cfg, "guidance", model)
+        self._export_fovy_deg = self._predict_fovy_deg(data)
         g = self.geometry
         dev = g.device
         H, W = int(data.height), int(data.width)
@@ -818,6 +859,14 @@ class SuGaRStatic(_SystemBase):
     def training_step(self):
         self.do_update_step(0, self.stage.global_step)
         return self.stage.iteration()
+
+    def export(self, out_dir, n_views=None, seed=0, chunk=8):
+        """The static system's predict epoch (C/system/base.py:72-323): ``<out_dir>/extracted_mesh.obj`` (+ .mtl, .png) of the canonical
+        mesh with the baked texture.  Returns the OBJ path."""
+        from . import texture_export as tx
+
+        atlas, texture = self.bake_texture(n_views, seed, chunk)
+        return tx.export_textured_mesh(out_dir, self.geometry, texture, atlas)
 
 
 def _nonzero(v):

@@ -223,3 +223,82 @@ def load_geometry(geometry, path, strict=False):
     sd, epoch, step = load_module_weights(path, module_name="geometry")
     res = geometry.load_state_dict(sd, strict=strict)
     return list(res.missing_keys), list(res.unexpected_keys), epoch, step
+
+
+# ------------------------------------------------------------------------------------------------ textured OBJ
+def encode_png(texture):
+    """PNG bytes of a texture [H,W,3]: float values are clamped to [0, 1] and rounded, round(clamp(t, 0, 1) * 255); uint8 is kept."""
+    import io
+
+    from PIL import Image
+
+    t = np.asarray(texture)
+    if t.dtype != np.uint8:
+        t = np.rint(np.clip(t.astype(np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
+    buf = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(t), "RGB").save(buf, format="PNG")
+    return buf.getvalue()
+
+
+def write_obj(path, verts, faces, verts_uvs, faces_uvs, texture):
+    """Textured OBJ in the layout of pytorch3d's ``save_obj`` (the reference's export, C/system/sugar_4dgen.py:629-636):
+    ``mtllib <stem>.mtl``, ``usemtl mesh``, ``v``, ``vt``, ``f v/vt`` (1-based), a sibling ``<stem>.mtl`` whose ``map_Kd`` names
+    ``<stem>.png``.  `texture`: [H,W,3] float in [0, 1] (clamped and rounded, ``encode_png``), uint8, or PNG bytes already encoded
+    (one encode for many files).  Differences from pytorch3d (unpinned): vertices and UVs are written with %.9g, so float32 values
+    survive the round trip (pytorch3d writes 6 decimals), and the PNG rounds where pytorch3d's writer truncates."""
+    import os
+
+    v = np.asarray(verts, np.float32).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    vt = np.asarray(verts_uvs, np.float32).reshape(-1, 2)
+    ft = np.asarray(faces_uvs, np.int64).reshape(-1, 3)
+    if len(ft) != len(f):
+        raise ValueError(f"write_obj: {len(f)} faces but {len(ft)} UV faces")
+    stem = os.path.splitext(os.path.basename(path))[0]
+    d = os.path.dirname(os.path.abspath(path))
+    fv = np.empty((len(f), 6), np.int64)
+    fv[:, 0::2], fv[:, 1::2] = f + 1, ft + 1
+    # one C-level % per block (no Python loop per vertex): float32 -> float64 is exact, %.9g round-trips float32
+    body = [f"mtllib {stem}.mtl\nusemtl mesh\n",
+            ("v %.9g %.9g %.9g\n" * len(v)) % tuple(v.astype(np.float64).ravel().tolist()),
+            ("vt %.9g %.9g\n" * len(vt)) % tuple(vt.astype(np.float64).ravel().tolist()),
+            ("f %d/%d %d/%d %d/%d\n" * len(fv)) % tuple(fv.ravel().tolist())]
+    with open(path, "w") as fh:
+        fh.write("".join(body))
+    with open(os.path.join(d, stem + ".mtl"), "w") as fh:
+        fh.write(f"newmtl mesh\nmap_Kd {stem}.png\nKa 1.000 1.000 1.000\nKd 1.000 1.000 1.000\nKs 0.000 0.000 0.000\n")
+    png = texture if isinstance(texture, (bytes, bytearray)) else encode_png(texture)
+    with open(os.path.join(d, stem + ".png"), "wb") as fh:
+        fh.write(png)
+
+
+def read_obj(path):
+    """The OBJ ``write_obj`` writes (v, vt, ``f v/vt`` triangles, the mtllib's map_Kd): {"verts" [V,3] float32, "faces" [F,3] int64,
+    "verts_uvs" [*,2] float32, "faces_uvs" [F,3] int64 (0-based), "texture" [H,W,3] uint8 or None}."""
+    import os
+
+    v, vt, fl, mtl = [], [], [], None
+    with open(path) as fh:
+        for line in fh:
+            if line.startswith("v "):
+                v.append(line[2:])
+            elif line.startswith("vt "):
+                vt.append(line[3:])
+            elif line.startswith("f "):
+                fl.append(line[2:].replace("/", " "))
+            elif line.startswith("mtllib "):
+                mtl = line[7:].strip()
+    num = lambda rows, dt, k: np.array(" ".join(rows).split(), dt).reshape(-1, k)
+    verts = num(v, np.float64, 3).astype(np.float32)
+    uvs = num(vt, np.float64, 2).astype(np.float32)
+    fi = num(fl, np.int64, 6) - 1
+    tex = None
+    if mtl is not None:
+        d = os.path.dirname(os.path.abspath(path))
+        with open(os.path.join(d, mtl)) as fh:
+            maps = [ln.split(None, 1)[1].strip() for ln in fh if ln.startswith("map_Kd ")]
+        if maps:
+            from PIL import Image
+
+            tex = np.asarray(Image.open(os.path.join(d, maps[0])).convert("RGB"))
+    return {"verts": verts, "faces": fi[:, 0::2], "verts_uvs": uvs, "faces_uvs": fi[:, 1::2], "texture": tex}

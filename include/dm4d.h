@@ -18,6 +18,8 @@
  *   dm4d_skin_*           C/geometry/dynamic_sugar.py:408-465,487-613 (+ C/utils/dual_quaternions.py)
  *   dm4d_face_gaussians_* C/geometry/dynamic_sugar.py:657-706,726-743,877-889,330-364 and
  *                         C/geometry/sugar.py:479-518
+ *   dm4d_tex_*, dm4d_mesh_raster  C/system/base.py:72-292 (texture baking of the export; pytorch3d's MeshRasterizer /
+ *                         TexturesUV, un-vendored, C/requirements.txt:46)
  *
  * Return convention: >= 0 success (some calls return a count), < 0 error code;
  * dm4d_last_error() returns a thread-local description.
@@ -45,7 +47,7 @@ typedef void *dm4d_stream_t;   /* hipStream_t */
 /* ABI version = 100 * major + round.  A binding built against this header checks dm4d_version() == DM4D_ABI_VERSION when it loads the
  * library (dreammesh4d_amd/_lib.py does).  Entry points are never changed in place from round 5 on: a new argument is a new symbol
  * (dm4d_adamw_step beside dm4d_adamw_message, dm4d_normal_consistency_backward_scratch beside dm4d_normal_consistency_backward). */
-#define DM4D_ABI_VERSION 105
+#define DM4D_ABI_VERSION 106
 int dm4d_version(void);
 const char *dm4d_last_error(void);
 /* Number of HIP devices visible / name of device `dev` (host helpers for the loader). */
@@ -888,6 +890,44 @@ int dm4d_step_backward_rgb(dm4d_step *s, const float *dL_dcolor, const float *dL
                            const float *dL_dvrot_ext, dm4d_stream_t stream);
 /* the object's dm4d_views as the last forward left it (for dm4d_views_counters); NULL if `s` is not a step object */
 const dm4d_views *dm4d_step_views(const dm4d_step *s);
+
+/* ------------------------------------------------------------------ texture baking (textured mesh export)
+ * The predict path of the sugar / dynamic-sugar systems (C/system/base.py:72-292, C/system/sugar_4dgen.py:594-640), whose mesh
+ * rasterization and texture sampling are pytorch3d's (MeshRasterizer, TexturesUV: un-vendored, C/requirements.txt:46).
+ * Atlas: faces paired into square_size^2-texel squares, face 2k = bottom triangle of square k, 2k+1 = its top triangle, squares
+ * row-major on an n x n grid, n = int(sqrt(F / 2 + 1) + 1), texture_size = square_size * n (C/system/base.py:78-131).
+ * Texture layout: [texture_size, texture_size, 3] float32 AFTER the reference's transpose and flip (:208-209); a texel index is
+ * row * texture_size + column of that image. */
+
+/* texture_size of the atlas of F faces (C/system/base.py:84-87); < 0 if F < 1 or square_size < 4. */
+int32_t dm4d_tex_atlas_size(int32_t F, int32_t square_size);
+/* Initial texture (C/system/base.py:133-209): every texel of a face's triangle gets SH2RGB of the DC coefficient of the face's
+ * Gaussian of highest density exp(-0.5 clamp(|(R diag(1/s))^T (p - mu)|^2, 0, 1e8)) at the texel's point p (first index on ties).
+ * verts [V,3], faces [F,3] int32 (the canonical surface mesh), means [F*G,3], rotations [F*G,4] (w,x,y,z), scales [F*G,3],
+ * sh_dc [F*G,3].  texture [T,T,3]: only the texels of the triangles are written -- the caller fills it with SH2RGB(0) = 0.5
+ * first (the reference's zero-initialised image).  square_size >= 4 (the barycentric formula divides by square_size - 3). */
+int dm4d_tex_atlas_init(int32_t F, int32_t G, int32_t square_size, const float *verts, const int32_t *faces, const float *means,
+                        const float *rotations, const float *scales, const float *sh_dc, float *texture, dm4d_stream_t stream);
+/* Scratch of dm4d_mesh_raster: the packed z-buffer [B,H,W] u64 and the list of large (view, face) pairs. */
+size_t dm4d_mesh_raster_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t F);
+/* MeshRasterizer (blur_radius 0, faces_per_pixel 1, no culling) + the nearest sample of the index texture
+ * (C/system/base.py:211-251,268-276) over B views: viewmatrix / projmatrix [B,16] as dm4d_raster_settings holds them (so pixel
+ * (x, y) is that of the Gaussian image of the same camera).  A pixel is covered by a face whose projected triangle contains
+ * its centre, edges included; the nearest view depth wins, the lower face id on equal (float32) depth; faces with a vertex at
+ * view depth <= 0.1 and zero-area faces are skipped.  texel [B,H,W] int32: the atlas texel of the covering face's
+ * perspective-correct UV (verts_uv [*,2], faces_uv [F,3] int32; nearest sample with align_corners and v flipped, as TexturesUV),
+ * -1 where uncovered.  face_out [B,H,W] int32 / bary_out [B,H,W,3] float: both NULL or both given (tests). */
+int dm4d_mesh_raster(int32_t B, int32_t H, int32_t W, int32_t F, const float *verts, const int32_t *faces, const float *viewmatrix,
+                     const float *projmatrix, const float *verts_uv, const int32_t *faces_uv, int32_t texture_size, void *scratch,
+                     size_t scratch_bytes, int32_t *texel, int32_t *face_out, float *bary_out, dm4d_stream_t stream);
+/* Claim words of dm4d_tex_accumulate: one u64 per texel.  Zero them ONCE when a bake starts; they need no clear between views. */
+size_t dm4d_tex_claim_bytes(int32_t n_texels);
+/* One view of the per-view texel update (C/system/base.py:278-292): among the view's pixels on one texel exactly one counts --
+ * here the lowest linear pixel index -- and adds rgb[c * channel_stride + pixel] into sum[texel, c] and 1 into count[texel]
+ * (the first visit's discarded initial colour is the caller's finish: count > 0 ? sum / count : initial).  texel [n_pixels]
+ * (-1 = skip), sum [n_texels,3], count [n_texels].  epoch: 1, 2, 3, ... one per call of a bake, strictly increasing. */
+int dm4d_tex_accumulate(int32_t n_pixels, const int32_t *texel, const float *rgb, int64_t channel_stride, uint32_t epoch, void *claim,
+                        size_t claim_bytes, int32_t n_texels, float *sum, float *count, dm4d_stream_t stream);
 
 #ifdef __cplusplus
 }
