@@ -79,7 +79,8 @@ def test_zero123_mirror_on_device_vs_reference_golden(dtype, tol_unet, tol_enc, 
     layers (thresholds lowered so that every supported shape takes them) and the fused norms; no convolution may fall back to
     the library (the dispatch counters of zero123._library_fallback).  The 4/8/16-wide attention heads of this reduced model
     are outside csrc/attention.hip's head sizes (40 / 64 / 80 / 160) and stay on the library: tests/test_attention_gpu.py
-    and the full-size bench cover that kernel."""
+    and tests/test_zero123_fullsize_gpu.py (the full-size model, every kernel call against float64 at the production
+    dispatch) cover that kernel."""
     _need_gpu()
     from dreammesh4d_amd import conv_mfma, fused_norm, zero123 as z
 
