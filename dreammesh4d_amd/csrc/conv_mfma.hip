@@ -52,13 +52,7 @@ struct ConvDesc {
     float *partial;                  // [splits][M][Cout] when splits > 1
     int splits, kt_total, kt_per;    // k-tiles (taps x Cin / 32) in all / per split
     int act;                         // epilogue: 0 none | 1 GEGLU: tile columns [0, 64) x gelu(columns [64, 128)), y is [M][Cout / 2] (dm4d_linear_f16)
-    int probe;                       // timing experiments only (-DDM4D_CONV_PROBE, env DM4D_CONV_PROBE): 1 no stores, 2 no MFMA, 4 no DMA
 };
-#ifdef DM4D_CONV_PROBE
-#define CV_PROBE(bit) (cv_probe & (bit))
-#else
-#define CV_PROBE(bit) false
-#endif
 
 // slot (16-byte unit) of piece c of row r in a stage's operand tile
 __device__ __forceinline__ int cv_slot(int r, int c) { return 4 * r + (c ^ ((r >> 2) & 3)); }
@@ -73,7 +67,7 @@ __device__ __forceinline__ int cv_slot(int r, int c) { return 4 * r + (c ^ ((r >
 //   (rounded again, like the separate residual add it replaces).
 template <int BM, int BN, int NW, int MB, int NB, class Pix>
 __device__ __forceinline__ void conv_epilogue(const ConvDesc &d, f32x16 (&acc)[MB][NB], const int (&row_of)[MB], int col0, int n0, char *stg, int tid,
-                                              int lane, [[maybe_unused]] int cv_probe, Pix pix)
+                                              int lane, Pix pix)
 {
     if (d.splits > 1) {
 #pragma unroll
@@ -85,7 +79,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvDesc &d, f32x16 (&acc)[M
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int co = n0 + col0 + 32 * j + 8 * q + 4 * (lane >> 5);
-                    if (co >= d.Cout || CV_PROBE(1)) continue;
+                    if (co >= d.Cout) continue;
                     *reinterpret_cast<float4 *>(d.partial + ((size_t)blockIdx.z * d.M + px) * d.Cout + co) =
                         make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
                 }
@@ -119,7 +113,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvDesc &d, f32x16 (&acc)[M
 #pragma unroll 2
             for (int row = tid / kOutPieces; row < BM; row += kRows) {
                 const int px = pix(row);
-                if (px < 0 || CV_PROBE(1)) continue;
+                if (px < 0) continue;
                 const f16x8 v = *reinterpret_cast<const f16x8 *>(stg + (size_t)row * kRowB + 16 * piece);
                 const f16x8 g = *reinterpret_cast<const f16x8 *>(stg + (size_t)row * kRowB + 16 * (piece + 8));
                 f16x8 o;
@@ -141,7 +135,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvDesc &d, f32x16 (&acc)[M
 #pragma unroll 4
     for (int row = tid / kPieces; row < BM; row += kRowsPerPass) {
         const int px = pix(row);
-        if (px < 0 || CV_PROBE(1)) continue;
+        if (px < 0) continue;
         f16x8 v = *reinterpret_cast<const f16x8 *>(stg + (size_t)row * kRowB + 16 * piece);
         const size_t o = (size_t)px * d.Cout + co;
         if (d.res) {
@@ -164,8 +158,6 @@ __device__ __forceinline__ void conv3x3_tile(const ConvDesc &d)
     constexpr int A_INSTR = (BM * 4 + 64 * NW - 1) / (64 * NW), B_INSTR = (BN * 4 + 64 * NW - 1) / (64 * NW);   // DMA instructions per wave and stage
     constexpr int A_SLOTS = A_INSTR * 64 * NW, B_SLOTS = B_INSTR * 64 * NW;         // 16-byte slots per stage (rows past BM / BN: padding)
     extern __shared__ __attribute__((aligned(1024))) uint4 smem[];                  // [stage][A_SLOTS + B_SLOTS]
-    [[maybe_unused]] const int cv_probe = d.probe;
-    if (CV_PROBE(8)) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);            // (provably wave-uniform: LDS-DMA bases stay in SGPRs)
     const int wm = wave % WM, wn = wave / WM;
@@ -217,15 +209,13 @@ __device__ __forceinline__ void conv3x3_tile(const ConvDesc &d)
     set_tap();
     constexpr int kStageSlots = A_SLOTS + B_SLOTS;
     auto issue = [&](int stage) {       // the next k-tile of the stream into `stage`
-        if (!(CV_PROBE(4))) {
-            uint4 *sa = smem + stage * kStageSlots, *sb = sa + A_SLOTS;
+        uint4 *sa = smem + stage * kStageSlots, *sb = sa + A_SLOTS;
 #pragma unroll
-            for (int i = 0; i < A_INSTR; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rs, (__attribute__((address_space(3))) void *)(sa + 64 * (wave * A_INSTR + i)), 16, a_cur[i], is_a, 0, 0);
+        for (int i = 0; i < A_INSTR; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rs, (__attribute__((address_space(3))) void *)(sa + 64 * (wave * A_INSTR + i)), 16, a_cur[i], is_a, 0, 0);
 #pragma unroll
-            for (int i = 0; i < B_INSTR; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rs, (__attribute__((address_space(3))) void *)(sb + 64 * (wave * B_INSTR + i)), 16, b_vo[i], is_b, 0, 0);
-        }
+        for (int i = 0; i < B_INSTR; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rs, (__attribute__((address_space(3))) void *)(sb + 64 * (wave * B_INSTR + i)), 16, b_vo[i], is_b, 0, 0);
         is_a += kCvBK * 2;
         is_b += kCvBK * 2;
         if (++is_chunk == cpt) {        // next tap: same channels from the start, the pixel one to the right (or a row down)
@@ -266,17 +256,16 @@ __device__ __forceinline__ void conv3x3_tile(const ConvDesc &d)
     }
     auto read = [&](auto KS, auto STAGE) {
         constexpr int ks = decltype(KS)::value, stage = decltype(STAGE)::value;
-        if (CV_PROBE(64)) return;
 #pragma unroll
         for (int i = 0; i < MB; ++i) ra[ks][i] = *reinterpret_cast<const __attribute__((address_space(3))) f16x8 *>(fa[ks][i] + stage * (kStageSlots * 16));
 #pragma unroll
         for (int j = 0; j < NB; ++j) rb[ks][j] = *reinterpret_cast<const __attribute__((address_space(3))) f16x8 *>(fb[ks][j] + stage * (kStageSlots * 16));
     };
     // the FILTER fragment is the MFMA's A operand: D[row = filter][col = pixel], so a lane ends up with 4 consecutive output
-    // channels of one pixel per register quad (the epilogue packs them)
-    auto mma = [&](auto KS) {
+    // channels of one pixel per register quad (the epilogue packs them).  (The captures are listed: their order sets the closure's layout,
+    // which steers the register assignment -- with [&] the same instructions come out on other registers.)
+    auto mma = [&acc, &ra, &rb](auto KS) {
         constexpr int ks = decltype(KS)::value;
-        if (CV_PROBE(2)) { acc[0][0][0] += (float)ra[ks][0][0] + (float)rb[ks][0][0]; return; }
 #pragma unroll
         for (int i = 0; i < MB; ++i)
 #pragma unroll
@@ -288,7 +277,7 @@ __device__ __forceinline__ void conv3x3_tile(const ConvDesc &d)
     constexpr int S = kCvStages;
     constexpr int kPerStage = A_INSTR + B_INSTR;          // DMA instructions a wave has in flight per k-tile
     static_assert(S >= 3 && S <= 6, "ring depth");
-    const int nk = CV_PROBE(16) ? 1 : kt1 - kt0;
+    const int nk = kt1 - kt0;
     // s_waitcnt vmcnt(tiles x kPerStage) for a run-time number of k-tiles allowed in flight (the immediate must be a constant)
     auto wait_tiles = [&](int fly) {
         switch (fly) {
@@ -313,7 +302,7 @@ __device__ __forceinline__ void conv3x3_tile(const ConvDesc &d)
         __builtin_amdgcn_sched_barrier(0);      // reads first, THEN the MFMAs they overlap with (the scheduler otherwise sinks them to 1-2 MFMAs before their use)
         mma(K0{});
         wait_tiles(min(S - 3, nk - 2 - t));     // tile t + 1 has landed; the tiles issued after it may be in flight
-        if (!CV_PROBE(32)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         if (t + S - 1 < nk) issue((u + S - 1) % S);
         read(K0{}, std::integral_constant<int, (u + 1) % S>{});
         __builtin_amdgcn_sched_barrier(0);
@@ -342,7 +331,7 @@ __device__ __forceinline__ void conv3x3_tile(const ConvDesc &d)
     if (nk > 0) run(t, nk - t, true);             // 1 .. S tiles left, starting in stage 0
 
     static_assert((size_t)BM * (BN * 2 + 16) <= (size_t)kCvStages * (A_SLOTS + B_SLOTS) * 16, "epilogue staging does not fit the ring");
-    conv_epilogue<BM, BN, NW>(d, acc, a_row, 32 * NB * wn, n0, reinterpret_cast<char *>(smem), tid, lane, cv_probe,
+    conv_epilogue<BM, BN, NW>(d, acc, a_row, 32 * NB * wn, n0, reinterpret_cast<char *>(smem), tid, lane,
                               [&](int row) {
                                   const int px = m0 + row;
                                   if (px >= d.M) return -1;
@@ -417,7 +406,6 @@ __device__ __forceinline__ void conv3x3_direct_tile(const ConvDesc &d, int chunk
     constexpr int kDirPieces = kDirPatchSlots / (64 * NW), kDirBSlots = 256 * NWN, kDirRing = RING, kDirAhead = AHEAD;
     static_assert(AHEAD >= 2 && AHEAD < RING && 9 % RING == 0 && kDirPieces <= 9, "ring");
     extern __shared__ __attribute__((aligned(1024))) uint4 smem[];
-    [[maybe_unused]] const int cv_probe = d.probe;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 3, wn = wave >> 2;
@@ -455,12 +443,10 @@ __device__ __forceinline__ void conv3x3_direct_tile(const ConvDesc &d, int chunk
     }
     const int cin2 = d.Cin * 2;
     auto issue_patch = [&](int piece, int buf, int chunk) {              // chunk: relative to ch0
-        if (CV_PROBE(4)) return;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rs, (__attribute__((address_space(3))) void *)(s_patch0 + buf * kPatchStride + 64 * (wave * kDirPieces + piece)),
                                                  16, p_vo[piece], (ch0 + chunk) * (kCvBK * 2), 0, 0);
     };
     auto issue_b = [&](int tap, int stage, int chunk) {
-        if (CV_PROBE(4)) return;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rs, (__attribute__((address_space(3))) void *)(s_b + stage * kDirBSlots + 64 * wave), 16, b_vo,
                                                  tap * cin2 + (ch0 + chunk) * (kCvBK * 2), 0, 0);
     };
@@ -498,7 +484,6 @@ __device__ __forceinline__ void conv3x3_direct_tile(const ConvDesc &d, int chunk
     // fragments of half step ks of tap TAP from patch buffer at byte address `pbase`, filter stage TAP % 3
     auto read = [&](auto KS, auto TAP, unsigned pbase) {
         constexpr int ks = decltype(KS)::value, tap = decltype(TAP)::value, dyi = tap / 3, dx = tap % 3 - 1;
-        if (CV_PROBE(64)) return;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int q = qa[i][dyi] + dx;
@@ -509,9 +494,8 @@ __device__ __forceinline__ void conv3x3_direct_tile(const ConvDesc &d, int chunk
         for (int j = 0; j < 2; ++j)
             rb[ks][j] = *reinterpret_cast<const __attribute__((address_space(3))) f16x8 *>(fb[ks][j] + (tap % kDirRing) * (kDirBSlots * 16));
     };
-    auto mma = [&](auto KS) {
+    auto mma = [&acc, &ra, &rb](auto KS) {         // (captures listed: see conv3x3_tile)
         constexpr int ks = decltype(KS)::value;
-        if (CV_PROBE(2)) { acc[0][0][0] += (float)ra[ks][0][0] + (float)rb[ks][0][0]; return; }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -541,7 +525,7 @@ __device__ __forceinline__ void conv3x3_direct_tile(const ConvDesc &d, int chunk
         // k-tile + 1's filters (and every patch piece issued before them) have landed
         if (more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(dir_in_flight(tap, true, kDirPieces, kDirAhead)) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(dir_in_flight(tap, false, kDirPieces, kDirAhead)) : "memory");
-        if (!CV_PROBE(32)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         if (tap < kDirPieces && more) issue_patch(tap, (ch + 1) & 1, ch + 1);
         if (tap + kDirAhead < 9) issue_b(tap + kDirAhead, (tap + kDirAhead) % kDirRing, ch);
         else if (more) issue_b(tap + kDirAhead - 9, (tap + kDirAhead - 9) % kDirRing, ch + 1);
@@ -570,7 +554,7 @@ __device__ __forceinline__ void conv3x3_direct_tile(const ConvDesc &d, int chunk
     }
 #undef DM4D_TAP
     static_assert((size_t)BM * (BN * 2 + 16) <= (size_t)dir_lds_slots<NWN, RING>() * 16, "epilogue staging does not fit");
-    conv_epilogue<BM, BN, NW>(d, acc, row_of, 64 * wn, n0, reinterpret_cast<char *>(smem), tid, lane, cv_probe, [&](int row) {
+    conv_epilogue<BM, BN, NW>(d, acc, row_of, 64 * wn, n0, reinterpret_cast<char *>(smem), tid, lane, [&](int row) {
         const int g = g0 + (row >> lgTW);
         return g < R ? g * W + x0 + (row & (TW - 1)) : -1;
     });
@@ -608,7 +592,6 @@ __device__ __forceinline__ void conv3x3_direct_pp_tile(const ConvDesc &d, int ch
     constexpr int kDirPieces = kDirPatchSlots / (64 * NW), kDirBSlots = 256 * NWN, kDirRing = RING, kDirAhead = AHEAD;
     static_assert(AHEAD >= 2 && AHEAD < RING && kDirPieces <= 9, "ring");
     extern __shared__ __attribute__((aligned(1024))) uint4 smem[];
-    [[maybe_unused]] const int cv_probe = d.probe;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 3, wn = wave >> 2;
@@ -644,12 +627,10 @@ __device__ __forceinline__ void conv3x3_direct_pp_tile(const ConvDesc &d, int ch
     }
     const int cin2 = d.Cin * 2;
     auto issue_patch = [&](int piece, int buf, int chunk) {
-        if (CV_PROBE(4)) return;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rs, (__attribute__((address_space(3))) void *)(s_patch0 + buf * kPatchStride + 64 * (wave * kDirPieces + piece)),
                                                  16, p_vo[piece], (ch0 + chunk) * (kCvBK * 2), 0, 0);
     };
     auto issue_b = [&](int tap, int stage, int chunk) {
-        if (CV_PROBE(4)) return;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rs, (__attribute__((address_space(3))) void *)(s_b + stage * kDirBSlots + 64 * wave), 16, b_vo,
                                                  tap * cin2 + (ch0 + chunk) * (kCvBK * 2), 0, 0);
     };
@@ -701,7 +682,6 @@ __device__ __forceinline__ void conv3x3_direct_pp_tile(const ConvDesc &d, int ch
     // every fragment of k-tile (tap TAP) from the patch buffer at byte address `pbase`, filter stage TAP % RING
     auto read_all = [&](auto TAP, unsigned pbase) {
         constexpr int tap = decltype(TAP)::value;
-        if (CV_PROBE(64)) return;
         unsigned pa[MB];
 #pragma unroll
         for (int i = 0; i < MB; ++i) {
@@ -738,7 +718,7 @@ __device__ __forceinline__ void conv3x3_direct_pp_tile(const ConvDesc &d, int ch
     if (wn == 1) __builtin_amdgcn_s_barrier();              // the second half starts one interval late: its LOAD beside the first half's COMPUTE
     // Measured alternatives (4 x 64^2, 512 -> 512, us per call; the lock-step kernel 78.7-81): the DMA issued in the LOAD interval 71.3; ONE
     // barrier per k-tile with the second half multiplying k-tile t - 1 BEFORE it loads k-tile t (an interval = one wave's LOAD + COMPUTE)
-    // 73.5; this form 68.3.  The matrix stream alone (no reads, no DMA) takes 54 us of the lock-step kernel's 87 in the probe build: the
+    // 73.5; this form 68.3.  The matrix stream alone (no reads, no DMA) takes 54 us of the lock-step kernel's 87 (round 6, a timing build): the
     // chip does not sustain the nominal 2.4 GHz x 1024 flop per SIMD cycle under it, so the ceiling is nearer 1.6 than 2.5 PFLOP/s.
     auto step = [&](auto TAP, int ch, unsigned pcur, bool more) {
         constexpr int tap = decltype(TAP)::value;
@@ -757,7 +737,7 @@ __device__ __forceinline__ void conv3x3_direct_pp_tile(const ConvDesc &d, int ch
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(dir_in_flight(tap, false, kDirPieces, kDirAhead) + kMine0) : "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        if (!CV_PROBE(32)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         // ---- COMPUTE: 4 MB MFMAs; MB = 2: the DMA of k-tile + AHEAD is issued between them
 #pragma unroll
@@ -766,8 +746,7 @@ __device__ __forceinline__ void conv3x3_direct_pp_tile(const ConvDesc &d, int ch
             for (int i = 0; i < MB; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    if (CV_PROBE(2)) acc[0][0][0] += (float)ra[ks][i][0] + (float)rb[ks][j][0];
-                    else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(rb[ks][j], ra[ks][i], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(rb[ks][j], ra[ks][i], acc[i][j], 0, 0, 0);
                     if constexpr (!kDmaInLoad) {
                         if (ks == 0 && i == 0 && j == 0) {
                             if (tap < kDirPieces && more) issue_patch(tap, (ch + 1) & 1, ch + 1);
@@ -779,7 +758,7 @@ __device__ __forceinline__ void conv3x3_direct_pp_tile(const ConvDesc &d, int ch
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-        if (!CV_PROBE(32)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     };
     for (int ch = 0; ch < nch; ++ch) {
@@ -798,7 +777,7 @@ __device__ __forceinline__ void conv3x3_direct_pp_tile(const ConvDesc &d, int ch
 #undef DM4D_TAP
     if (wn == 0) __builtin_amdgcn_s_barrier();              // (the second half's last COMPUTE)
     static_assert((size_t)BM * (BN * 2 + 16) <= (size_t)pp_lds_slots<MB>() * 16, "epilogue staging does not fit");
-    conv_epilogue<BM, BN, NW>(d, acc, row_of, 64 * wn, n0, reinterpret_cast<char *>(smem), tid, lane, cv_probe, [&](int row) {
+    conv_epilogue<BM, BN, NW>(d, acc, row_of, 64 * wn, n0, reinterpret_cast<char *>(smem), tid, lane, [&](int row) {
         const int g = g0 + (row >> lgTW);
         return g < R ? g * W + x0 + (row & (TW - 1)) : -1;
     });
@@ -808,192 +787,6 @@ template <int AHEAD, int MB>
 __global__ __launch_bounds__(512) void k_conv3x3_direct_pp(ConvDesc d, int chunks_per_split, int lgTW)
 {
     conv3x3_direct_pp_tile<AHEAD, MB>(d, chunks_per_split, lgTW);
-}
-
-// ---------------------------------------------------------------------------------------- direct variant, rolled tap loop
-// The unrolled template above keeps every tap's swizzled fragment address in a register for the whole kernel (~130 of its 227 VGPRs):
-// two waves per SIMD, whose LDS reads, DMA issue and MFMAs then hardly overlap.  Here the SAME tile algebra for a 256-pixel x 64-filter
-// workgroup of 4 waves with the tap loop ROLLED over the three taps of a row (the row loop unrolled: which of a lane's three patch rows a
-// tap reads stays a compile-time register choice), the fragment addresses computed at each use (~6 VALU operations per 16-byte read, beside
-// 8 MFMAs per k-tile), a 3-stage filter ring (stage = column of the tap) fetched 2 ahead, and ONE patch buffer, re-fetched behind a
-// barrier at the chunk boundary: 37 KB of LDS and <= 128 registers -- FOUR workgroups per CU, which hide each other's boundaries and
-// whose LDS reads overlap with each other's MFMAs.
-template <int kRing, int kAhead>
-__device__ __forceinline__ void conv3x3_direct4_tile(const ConvDesc &d, int chunks_per_split, int lgTW)
-{
-    constexpr int BM = 256, BN = 64, NW = 4;
-    constexpr int kPieces = kDirPatchSlots / (64 * NW), kBSlots = 256;
-    static_assert(kAhead >= 2 && kAhead <= 9 && kRing >= kAhead + 1, "ring");
-    extern __shared__ __attribute__((aligned(1024))) uint4 smem[];
-    [[maybe_unused]] const int cv_probe = d.probe;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave;
-    const int W = d.W, TW = 1 << lgTW, PW = TW + 2, TH = BM >> lgTW, R = d.N * d.H;
-    const int ncb = W >> lgTW, rblk = blockIdx.x / ncb, cb = blockIdx.x - rblk * ncb;
-    const int g0 = rblk * TH, x0 = cb << lgTW, n0 = blockIdx.y * BN;
-    const int cpt = d.Cin / kCvBK;
-    const int ch0 = blockIdx.z * chunks_per_split, nch = min(cpt, ch0 + chunks_per_split) - ch0;
-    const int patch_px = (TH + 2) * PW;
-    constexpr unsigned kOob = 0x80000000u;
-    // LDS: [zeros | patch | filter ring]
-    uint4 *const s_patch = smem + kDirZeroSlots;
-    uint4 *const s_b = smem + kDirZeroSlots + kDirPatchSlots;             // [kRing][kBSlots]
-    if (tid < kDirZeroSlots) smem[tid] = make_uint4(0u, 0u, 0u, 0u);
-    const auto a_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(d.x) - (size_t)(W + 1) * d.Cin, 0,
-                                                        (int)(((size_t)d.M + 2 * W + 2) * d.Cin * 2), 0x00020000);
-    const auto b_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(d.w), 0, (int)((size_t)d.Cout * 9 * d.Cin * 2), 0x00020000);
-    unsigned p_vo[kPieces];
-#pragma unroll
-    for (int i = 0; i < kPieces; ++i) {
-        const int s = 64 * (wave * kPieces + i) + lane, q = s >> 2, c = (s & 3) ^ ((q >> 2) & 3);
-        const int pr = q / PW, pc = q - pr * PW;
-        const int g = g0 - 1 + pr, x = x0 - 1 + pc;
-        const bool ok = q < patch_px && (unsigned)x < (unsigned)W && (unsigned)g < (unsigned)R;
-        p_vo[i] = ok ? (unsigned)((g + 1) * W + x + 1) * (unsigned)(d.Cin * 2) + 16u * c : kOob;
-    }
-    unsigned b_vo;
-    {
-        const int s = 64 * wave + lane, r = s >> 2, c = (s & 3) ^ ((r >> 2) & 3);
-        const int co = n0 + r;
-        b_vo = co < d.Cout ? (unsigned)co * (unsigned)(9 * d.Cin * 2) + 16u * c : kOob;
-    }
-    const int cin2 = d.Cin * 2;
-    auto issue_patch = [&](int piece, int chunk) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rs, (__attribute__((address_space(3))) void *)(s_patch + 64 * (wave * kPieces + piece)), 16, p_vo[piece],
-                                                 (ch0 + chunk) * (kCvBK * 2), 0, 0);
-    };
-    auto issue_b = [&](int tap, int stage, int chunk) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rs, (__attribute__((address_space(3))) void *)(s_b + stage * kBSlots + 64 * wave), 16, b_vo,
-                                                 tap * cin2 + (ch0 + chunk) * (kCvBK * 2), 0, 0);
-    };
-    int row_of[2], qa[2][3];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int r = 64 * wm + 32 * i + (lane & 31), tr = r >> lgTW, tc = r & (TW - 1);
-        const int g = g0 + tr, y = g % d.H;
-        const bool row_ok = g < R;
-        const int q = (tr + 1) * PW + tc + 1;
-        row_of[i] = r;
-        qa[i][0] = (row_ok && y > 0) ? q - PW : -2;
-        qa[i][1] = row_ok ? q : -2;
-        qa[i][2] = (row_ok && y < d.H - 1) ? q + PW : -2;
-    }
-    const int hi = lane >> 5;
-    unsigned fb[2][2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            fb[ks][j] = (unsigned)(size_t)(__attribute__((address_space(3))) uint4 *)(s_b + cv_slot(32 * j + (lane & 31), 2 * ks + hi));
-    const unsigned pb0 = (unsigned)(size_t)(__attribute__((address_space(3))) uint4 *)s_patch;
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    f16x8 ra[2][2] = {}, rb[2][2] = {};
-    // fragments of half step ks: patch pixels q0 / q1 (tap shift applied), filter ring stage `stage`
-    auto read = [&](auto KS, int q0, int q1, int stage) {
-        constexpr int ks = decltype(KS)::value;
-        const int qq[2] = {q0, q1};
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int q = qq[i];
-            const unsigned a = pb0 + 16u * (unsigned)(4 * q + ((2 * ks + hi) ^ ((q >> 2) & 3)));
-            ra[ks][i] = *reinterpret_cast<const __attribute__((address_space(3))) f16x8 *>(a);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            rb[ks][j] = *reinterpret_cast<const __attribute__((address_space(3))) f16x8 *>(fb[ks][j] + (unsigned)stage * (kBSlots * 16));
-    };
-    auto mma = [&](auto KS) {
-        constexpr int ks = decltype(KS)::value;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(rb[ks][j], ra[ks][i], acc[i][j], 0, 0, 0);
-    };
-    using K0 = std::integral_constant<int, 0>;
-    using K1 = std::integral_constant<int, 1>;
-
-    // k-tile t = (chunk t / 9, tap t % 9) lives in ring stage t % kRing; tiles t + 1 .. t + kAhead - 1 are in flight while t is multiplied
-    const int T = nch * 9;
-    if (nch > 0) {
-#pragma unroll
-        for (int i = 0; i < kPieces; ++i) issue_patch(i, 0);
-#pragma unroll
-        for (int k = 0; k < kAhead; ++k)
-            if (k < T) issue_b(k % 9, k % kRing, k / 9);
-        if (T >= kAhead) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kAhead - 1) : "memory");      // the patch and tile 0 have landed (in order)
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();                                                       // (also publishes the zero region)
-    if (nch > 0) read(K0{}, qa[0][0] - 1, qa[1][0] - 1, 0);
-    int t = 0, st_cur = 0, st_iss = kAhead % kRing, tap_iss = kAhead % 9, ch_iss = kAhead / 9;      // tile being multiplied; stage / (tap, chunk) of tile t + kAhead
-    for (int ch = 0; ch < nch; ++ch) {
-        const bool more = ch + 1 < nch;
-        // the three taps of patch row DY (compile time), rolled over the column dxi = 0, 1, 2 (tap = 3 DY + dxi, ring stage = dxi)
-        auto row = [&](auto DY) {
-            constexpr int dy = decltype(DY)::value;
-#pragma unroll 1
-            for (int dxi = 0; dxi < 3; ++dxi) {
-                const int tap = 3 * dy + dxi;
-                const bool final_tile = !more && tap == 8;
-                const int st_next = st_cur + 1 == kRing ? 0 : st_cur + 1;
-                read(K1{}, qa[0][dy] + dxi - 1, qa[1][dy] + dxi - 1, st_cur);
-                __builtin_amdgcn_sched_barrier(0);
-                mma(K0{});
-                if (!final_tile) {
-                    // k-tile + 1's filters have landed: of the kAhead - 1 tiles in flight the youngest kAhead - 2 may stay (the DMA retires in
-                    // order); near the end of the stream fewer are in flight and the count is no measure: wait for all
-                    if (t + kAhead - 1 < T) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kAhead - 2) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                    if (t + kAhead < T) issue_b(tap_iss, st_iss, ch_iss);            // k-tile + kAhead goes into a stage every wave has left
-                    if (tap != 8) {
-                        constexpr int dyn = dy < 2 ? dy + 1 : 2;
-                        const bool wrap = dxi == 2;
-                        read(K0{}, wrap ? qa[0][dyn] - 1 : qa[0][dy] + dxi, wrap ? qa[1][dyn] - 1 : qa[1][dy] + dxi, st_next);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                mma(K1{});
-                __builtin_amdgcn_sched_barrier(0);
-                ++t;
-                st_cur = st_next;
-                st_iss = st_iss + 1 == kRing ? 0 : st_iss + 1;
-                if (++tap_iss == 9) { tap_iss = 0; ++ch_iss; }
-            }
-        };
-        row(std::integral_constant<int, 0>{});
-        row(std::integral_constant<int, 1>{});
-        row(std::integral_constant<int, 2>{});
-        if (more) {
-            // every wave is done with the chunk's patch -> the next chunk's -> first fragments of its tap 0 (the CU's other workgroups
-            // run their taps meanwhile)
-            __builtin_amdgcn_s_barrier();
-#pragma unroll
-            for (int i = 0; i < kPieces; ++i) issue_patch(i, ch + 1);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            read(K0{}, qa[0][0] - 1, qa[1][0] - 1, st_cur);
-        }
-    }
-    static_assert((size_t)BM * (BN * 2 + 16) <= (size_t)(kDirZeroSlots + kDirPatchSlots + kRing * kBSlots) * 16, "epilogue staging does not fit");
-    conv_epilogue<BM, BN, NW>(d, acc, row_of, 0, n0, reinterpret_cast<char *>(smem), tid, lane, cv_probe, [&](int row) {
-        const int g = g0 + (row >> lgTW);
-        return g < R ? g * W + x0 + (row & (TW - 1)) : -1;
-    });
-}
-
-template <int kRing, int kAhead, int kOcc>
-__global__ __launch_bounds__(256, kOcc) void k_conv3x3_direct4(ConvDesc d, int chunks_per_split, int lgTW)
-{
-    conv3x3_direct4_tile<kRing, kAhead>(d, chunks_per_split, lgTW);
 }
 
 // y = sum over splits of partial + bias (+ res), 8 outputs per thread
@@ -1078,61 +871,55 @@ __global__ __launch_bounds__(256) void k_conv3x3_c128_small(int N, int H, int W,
     }
 }
 
-// tile configurations (DM4D_CONV_CFG; 3 and 7 are what conv_plan picks, the others are the measured alternatives of
-// profiles/r03_zero123.md): 3: 128 x 128, 4 waves of 64 x 64, 4-deep ring | 0 / 10 / 11: the same 3- / 5- / 6-deep | 4 / 6: 128 x 128,
-// 8 waves of 32 x 64, 3- / 4-deep | 7: the direct kernel, 256 x 128, 8 waves | 9: the direct kernel, 256 x 64, 4 waves, two per CU |
-// 12: the rolled-tap direct kernel, 256 x 64, four per CU | 13 (round 6, the default direct kernel): 7's tile with the two waves of a SIMD half a period apart |
-// 14: the same with a 512 x 128 tile (the plan's choice where its grid fills the machine).
-// (256 x 128 implicit-GEMM tiles with 64 x 64 or 128 x 64 wave tiles were tried and removed: 256 VGPRs with spills.)
-static void cfg_tile(int cfg, int &BM, int &BN)
+// tile configurations: 3: the implicit GEMM, 128 x 128, 4 waves of 64 x 64, 4-deep ring | 7: the direct kernel, 256 x 128, 8 waves in lock-step
+// (the bit-exact oracle of 13 / 14: tests/test_conv_mfma_gpu.py) | 13 (round 6, the default direct kernel): 7's tile with the two waves of a SIMD
+// half a period apart | 14: the same with a 512 x 128 tile (the plan's choice where its grid fills the machine).
+// Measured and removed (profiles/r03_zero123.md): the implicit GEMM with a 3- / 5- / 6-deep ring or with 8 waves of 32 x 64; the direct kernel
+// with 256 x 64 tiles of 4 waves (two workgroups per CU, or a rolled tap loop and four per CU); 256 x 128 implicit-GEMM tiles with 64 x 64 or
+// 128 x 64 wave tiles (256 VGPRs with spills).
+static bool is_direct(int cfg) { return cfg == 7 || cfg == 13 || cfg == 14; }
+static int cfg_tile_m(int cfg) { return cfg == 14 ? 512 : is_direct(cfg) ? 256 : 128; }      // (every configuration's tile is 128 filters wide)
+
+// A forced choice among the shipped kernels, for the tests and the tuning tools: DM4D_CONV_CFG / DM4D_CONV_SPLITS (conv_plan),
+// DM4D_LIN_CFG / DM4D_LIN_SPLITS (linear_plan).  Read per call: the conv test flips them within one process.  false: unset.
+static bool forced_plan(const char *name, int &v)
 {
-    BM = cfg == 14 ? 512 : (cfg == 7 || cfg == 9 || cfg == 12 || cfg == 13) ? 256 : 128;
-    BN = (cfg == 9 || cfg == 12) ? 64 : 128;
+    const char *e = getenv(name);
+    if (e) v = atoi(e);
+    return e != nullptr;
 }
-// (A/B switches, read once: the problem size from which the direct kernel takes the narrow images, the k-tiles a split must keep)
-static double direct_gflop() { static const double v = [] { const char *e = getenv("DM4D_CONV_DIRECT_GFLOP"); return e ? atof(e) : 14.0; }(); return v; }
-static int split_min_kt() { static const int v = [] { const char *e = getenv("DM4D_CONV_SPLIT_MIN_KT"); return e ? atoi(e) : 30; }(); return v; }
+
+// the direct kernel takes the VAE encoder's wide images (W >= 64: 1.3-1.5x the implicit GEMM per shape) and, of the narrow ones, the
+// problems of >= 14 GFLOP.  That threshold is set IN THE STEP (tools/sds_ab.py, thresholds of 0 / 3 / 7 / 14 / 28 / 1000 GFLOP on one
+// box: 10.60 / 10.51 / 10.59 / 10.42-10.49 / 10.83 / 10.78 ms per SDS step): timed alone (tools/conv_shapes.py) the split-K implicit GEMM
+// wins up to 28 GFLOP by up to 25 %, but in the step its float32 partial sums and second launch cost more than on an idle, cache-warm chip
+constexpr double kDirectGflop = 14.0;
+// the 512-pixel ping-pong tile where its grid still gives every CU a workgroup (the VAE encoder's 256^2 and 128^2 levels: -8 ... -12 % per call
+// against the 256-pixel one; with half the machine filled, 64^2: +20 ... +40 %)
+constexpr long kPp512MinWgs = 256;
+// split K only until every CU has ONE workgroup, and never below 30 k-tiles per workgroup: the float32 partial sums cost
+// splits x M x C_out x 8 bytes of traffic and a second launch (measured optimum on the UNet's 4^2 .. 16^2 levels,
+// tools/scratch/conv_splits.py: 12 / 24 splits at 4^2, 6 at 8^2, 3 at 16^2, none at 32^2)
+constexpr int kSplitWgs = 256;
+constexpr int kSplitMinKt = 30;
 static int conv_plan(int M, int W, int Cout, int kt_total, int &cfg, int &splits)
 {
-    const char *force = getenv("DM4D_CONV_CFG");          // (A/B switches, read per call: tools/conv_probe.py flips them within a process)
-    if (force) cfg = atoi(force);
-    // the direct kernel takes the VAE encoder's wide images (W >= 64: 1.3-1.5x the implicit GEMM per shape) and, of the narrow ones, the
-    // problems of >= 14 GFLOP.  That threshold is set IN THE STEP (tools/sds_ab.py, DM4D_CONV_DIRECT_GFLOP = 0 / 3 / 7 / 14 / 28 / 1000 on one
-    // box: 10.60 / 10.51 / 10.59 / 10.42-10.49 / 10.83 / 10.78 ms per SDS step): timed alone (tools/conv_shapes.py) the split-K implicit GEMM
-    // wins up to 28 GFLOP by up to 25 %, but in the step its float32 partial sums and second launch cost more than on an idle, cache-warm chip
-    else if (W >= 8 && (W & (W - 1)) == 0 && (W >= 64 || (double)M * Cout * kt_total * kCvBK * 2.0 >= direct_gflop() * 1e9)) {
-        // round 6: the ping-pong kernel (13) on every direct shape -- per call -4 ... -17 % against the lock-step 8-wave kernel (7) and
-        // -7 / +1 / -6 % against the rolled 4-wave one (12) on its three shapes (tools/conv_cfg_vae.py); in the step 67.1 -> 63.6 ms of direct
-        // convolutions per 21 steps under rocprofv3, 9.87 -> 9.78 ms per SDS step (tools/sds_ab.py, two alternating rounds)
-        static const int dcfg = [] { const char *e = getenv("DM4D_CONV_DIRECT_CFG"); return e ? atoi(e) : 13; }();      // (A/B switch: 7, 9, 12 or 13)
-        cfg = (dcfg == 7 || dcfg == 9 || dcfg == 12) ? dcfg : 13;
-        // the rolled-tap variant (four 4-wave workgroups per CU) where the grid gives every CU at least four 256 x 64 tiles: the VAE
-        // encoder's 256^2 and 128^2 levels (-12 / -10 / -4 % per call, tools/conv_cfg_vae.py); below that its chunk-boundary patch
-        // fetch is exposed and the 8-wave kernel wins (64^2: +6 ... +10 %)
-        static const long d4_min = [] { const char *e = getenv("DM4D_CONV_D4_MIN_WGS"); return e ? atol(e) : 1024L; }();      // (A/B switch; 0: never)
-        if (cfg == 7 && d4_min > 0 && (long)((M + 255) / 256) * ((Cout + 63) / 64) >= d4_min) cfg = 12;
-        // the 512-pixel ping-pong tile where its grid still gives every CU a workgroup (the VAE encoder's 256^2 and 128^2 levels: -8 ... -12 % per call
-        // against the 256-pixel one; with half the machine filled, 64^2: +20 ... +40 %)
-        static const long p14_min = [] { const char *e = getenv("DM4D_CONV_PP512_MIN_WGS"); return e ? atol(e) : 256L; }();      // (A/B switch; 0: never)
-        if (cfg == 13 && p14_min > 0 && W >= 32 && (long)((M + 511) / 512) * ((Cout + 127) / 128) >= p14_min) cfg = 14;
+    if (!forced_plan("DM4D_CONV_CFG", cfg)) {
+        if (W >= 8 && (W & (W - 1)) == 0 && (W >= 64 || (double)M * Cout * kt_total * kCvBK * 2.0 >= kDirectGflop * 1e9)) {
+            // round 6: the ping-pong kernel (13) on every direct shape -- per call -4 ... -17 % against the lock-step 8-wave kernel (7) and
+            // -7 / +1 / -6 % against round 4's rolled-tap 4-wave one on its three shapes (tools/conv_cfg_vae.py); in the step 67.1 -> 63.6 ms
+            // of direct convolutions per 21 steps under rocprofv3, 9.87 -> 9.78 ms per SDS step (tools/sds_ab.py, two alternating rounds)
+            cfg = 13;
+            if (W >= 32 && (long)((M + 511) / 512) * ((Cout + 127) / 128) >= kPp512MinWgs) cfg = 14;
+        }
+        else cfg = 3;
     }
-    else cfg = 3;
-    int BM, BN;
-    cfg_tile(cfg, BM, BN);
-    const long tiles = (long)((M + BM - 1) / BM) * ((Cout + BN - 1) / BN);
-    splits = 1;
-    const char *fs = getenv("DM4D_CONV_SPLITS");
-    if (fs) splits = atoi(fs);
-    else {
-        // split K only until every CU has ONE workgroup, and never below 30 k-tiles per workgroup: the float32 partial sums cost
-        // splits x M x C_out x 8 bytes of traffic and a second launch (measured optimum on the UNet's 4^2 .. 16^2 levels,
-        // tools/scratch/conv_splits.py: 12 / 24 splits at 4^2, 6 at 8^2, 3 at 16^2, none at 32^2)
-        static const int wgs = [] { const char *e = getenv("DM4D_CONV_SPLIT_WGS"); return e ? atoi(e) : 256; }();      // (A/B switch)
-        splits = (int)(wgs / tiles);
-        if (splits > kt_total / split_min_kt()) splits = kt_total / split_min_kt();
+    const int BM = cfg_tile_m(cfg);
+    const long tiles = (long)((M + BM - 1) / BM) * ((Cout + 127) / 128);
+    if (!forced_plan("DM4D_CONV_SPLITS", splits)) {
+        splits = (int)(kSplitWgs / tiles);
+        if (splits > kt_total / kSplitMinKt) splits = kt_total / kSplitMinKt;
     }
-    static const int max_splits = [] { const char *e = getenv("DM4D_CONV_MAX_SPLITS"); return e ? atoi(e) : 64; }();      // (A/B switch)
-    if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
     if (splits > 64) splits = 64;
     return 0;
@@ -1168,7 +955,7 @@ static inline int conv_out(int in, int stride, int pad) { return stride == 1 ? i
 static int conv_plan_s(int M, int W, int Cout, int kt_total, int stride, int &cfg, int &splits)
 {
     const int rc = conv_plan(M, stride == 1 ? W : 0, Cout, kt_total, cfg, splits);
-    if (stride != 1 && (cfg == 7 || cfg == 9 || cfg == 12 || cfg == 13 || cfg == 14)) cfg = 3;
+    if (stride != 1 && is_direct(cfg)) cfg = 3;
     return rc;
 }
 
@@ -1222,13 +1009,9 @@ int dm4d_conv3x3_strided_nhwc_f16(int32_t N, int32_t Hin, int32_t Win, int32_t C
     d.y = (_Float16 *)y;
     d.kt_total = 9 * Cin / kCvBK;
     d.act = 0;
-    d.probe = 0;
-#ifdef DM4D_CONV_PROBE
-    if (const char *pe = getenv("DM4D_CONV_PROBE")) d.probe = atoi(pe);
-#endif
     int cfg;
     conv_plan_s(d.M, W, Cout, d.kt_total, stride, cfg, d.splits);
-    if ((cfg == 7 || cfg == 9 || cfg == 12 || cfg == 13 || cfg == 14) && (stride != 1 || pad != 1)) { set_error("conv3x3: the direct kernel takes stride 1, pad 1 only"); return DM4D_ERR_UNSUPPORTED; }
+    if (is_direct(cfg) && (stride != 1 || pad != 1)) { set_error("conv3x3: the direct kernel takes stride 1, pad 1 only"); return DM4D_ERR_UNSUPPORTED; }
     d.kt_per = (d.kt_total + d.splits - 1) / d.splits;
     d.splits = (d.kt_total + d.kt_per - 1) / d.kt_per;
     d.partial = (float *)scratch;
@@ -1236,13 +1019,8 @@ int dm4d_conv3x3_strided_nhwc_f16(int32_t N, int32_t Hin, int32_t Win, int32_t C
     hipStream_t st = (hipStream_t)stream;
     int rc;
     switch (cfg) {
-    case 0: rc = conv_launch<2, 2, 2, 2, 3>(d, st); break;
     case 3: rc = conv_launch<2, 2, 2, 2, 4>(d, st); break;
-    case 10: rc = conv_launch<2, 2, 2, 2, 5>(d, st); break;      // 128 x 128, 4 waves, 5-deep (80 KB: two workgroups per CU)
-    case 11: rc = conv_launch<2, 2, 2, 2, 6>(d, st); break;      // ... 6-deep (96 KB: one workgroup per CU)
-    case 4: rc = conv_launch<4, 2, 1, 2, 3>(d, st); break;
-    case 6: rc = conv_launch<4, 2, 1, 2, 4>(d, st); break;
-    case 7: case 9: case 12: case 13: case 14: {      // direct: 256 pixels x 128 (7) / 64 (9) filters, the input patch resident in LDS for the nine taps
+    case 7: case 13: case 14: {      // direct: 256 (512: 14) pixels x 128 filters, the input patch resident in LDS for the nine taps
         const int W_ = d.W;
         if (W_ < 8 || (W_ & (W_ - 1)) != 0) { set_error("conv3x3 direct: W must be a power of two >= 8"); return DM4D_ERR_UNSUPPORTED; }
         int lgTW = 3;
@@ -1262,21 +1040,11 @@ int dm4d_conv3x3_strided_nhwc_f16(int32_t N, int32_t Hin, int32_t Win, int32_t C
             static bool attr_set = false;
             if (!attr_set) { DM4D_HIP_CHECK(hipFuncSetAttribute((const void *)k_conv3x3_direct_pp<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr_set = true; }
             hipLaunchKernelGGL((k_conv3x3_direct_pp<4, 2>), dim3(tiles_m, (d.Cout + 127) / 128, d.splits), dim3(512), lds, st, d, chunks_per_split, lgTW);
-        } else if (cfg == 7) {         // 8 waves, 256 x 128, one workgroup per CU
+        } else {                       // 7: 8 waves, 256 x 128, one workgroup per CU
             const size_t lds = (size_t)dir_lds_slots<2, 9>() * 16;
             static bool attr_set = false;
             if (!attr_set) { DM4D_HIP_CHECK(hipFuncSetAttribute((const void *)k_conv3x3_direct<2, 9, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr_set = true; }
             hipLaunchKernelGGL((k_conv3x3_direct<2, 9, 4>), dim3(tiles_m, (d.Cout + 127) / 128, d.splits), dim3(512), lds, st, d, chunks_per_split, lgTW);
-        } else if (cfg == 12) { // 4 waves, 256 x 64, rolled tap loop, one patch buffer: four workgroups per CU
-            const size_t lds = (size_t)(kDirZeroSlots + kDirPatchSlots + 3 * 256) * 16;
-            static bool attr_set = false;
-            if (!attr_set) { DM4D_HIP_CHECK(hipFuncSetAttribute((const void *)k_conv3x3_direct4<3, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr_set = true; }
-            hipLaunchKernelGGL((k_conv3x3_direct4<3, 2, 4>), dim3(tiles_m, (d.Cout + 63) / 64, d.splits), dim3(256), lds, st, d, chunks_per_split, lgTW);
-        } else {                // 4 waves, 256 x 64, two workgroups per CU (one fills the bubble around the other's barrier)
-            const size_t lds = (size_t)dir_lds_slots<1, 3>() * 16;
-            static bool attr_set = false;
-            if (!attr_set) { DM4D_HIP_CHECK(hipFuncSetAttribute((const void *)k_conv3x3_direct<1, 3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr_set = true; }
-            hipLaunchKernelGGL((k_conv3x3_direct<1, 3, 2>), dim3(tiles_m, (d.Cout + 63) / 64, d.splits), dim3(256), lds, st, d, chunks_per_split, lgTW);
         }
         DM4D_HIP_CHECK(hipGetLastError());
         rc = DM4D_OK;
@@ -1305,12 +1073,13 @@ static void linear_plan(int64_t M, int N, int kt_total, int act, int &cfg, int &
     // (tools/linear_tune.py: the 64 x 64 tiles win while the 128 x 128 ones would leave CUs idle -- unless K is long, where the larger
     // tile's fewer operand fetches matter more)
     cfg = (act != 1 && tiles128 < 200 && (kt_total <= 24 || (tiles128 < 96 && !(tiles128 >= 32 && kt_total >= 128)))) ? 13 : 3;      // (K >= 4096 on >= 32 tiles: 128 x 128 + split K)
-    if (const char *force = getenv("DM4D_LIN_CFG")) { const int f = atoi(force); if (act != 1 || f == 3) cfg = f; }
+    int f;
+    if (forced_plan("DM4D_LIN_CFG", f) && (act != 1 || f == 3)) cfg = f;
     const int B = cfg == 13 ? 64 : 128;
     const long tiles = (long)((M + B - 1) / B) * ((N + B - 1) / B);
     splits = (int)(256 / tiles);
     if (splits > kt_total / 30) splits = kt_total / 30;
-    if (const char *fs = getenv("DM4D_LIN_SPLITS")) splits = atoi(fs);
+    forced_plan("DM4D_LIN_SPLITS", splits);
     if (splits < 1 || act == 1) splits = 1;             // (the reduction kernel has no GEGLU)
     if (splits > 64) splits = 64;
 }
@@ -1342,7 +1111,6 @@ int dm4d_linear_f16(int64_t M, int32_t K, int32_t N, const void *x, const void *
     d.y = (_Float16 *)y;
     d.kt_total = K / kCvBK;
     d.act = act;
-    d.probe = 0;
     int cfg;
     linear_plan(M, N, d.kt_total, act, cfg, d.splits);
     d.kt_per = (d.kt_total + d.splits - 1) / d.splits;
@@ -1393,7 +1161,7 @@ int dm4d_conv3x3_s2_dgrad_nhwc_f16(int32_t N, int32_t Hin, int32_t Win, int32_t 
     d.ostep = 2; d.oy0 = 0; d.ox0 = 0;
     d.x = (const _Float16 *)dy; d.w = nullptr; d.bias = nullptr; d.res = nullptr; d.y = (_Float16 *)dx;
     d.partial = nullptr; d.splits = 1; d.kt_total = d.kt_per = 0;
-    d.act = 0; d.probe = 0;
+    d.act = 0;
     for (int c = 0; c < 4; ++c) a.w[c] = (const _Float16 *)w_cls[c];
     constexpr size_t lds = (size_t)4 * (2 + 2) * 256 * 16;                          // the 128 x 128 x 4-deep ring of conv_launch<2, 2, 2, 2, 4>
     static bool attr_set = false;

@@ -22,7 +22,6 @@
 // dz = dy silu'(z),  s1 = sum_group dz gamma,  s2 = sum_group dz gamma xhat,  m = elements per group:
 //     dx = rstd (dz gamma - (s1 + xhat s2) / m)
 // -- the same two-pass structure.
-#include <stdlib.h>
 #include <type_traits>
 #include "common.h"
 #include "dm4d.h"
@@ -343,8 +342,6 @@ __global__ __launch_bounds__(kSlabThreads) void k_groupnorm_slab_f16(GnArgs a, i
 // groups per workgroup, pieces per pixel and threads of the slab kernel for this shape; false: take the two-pass kernels
 static bool gn_slab_plan(const GnArgs &a, int &gb, int &ppp, int &threads)
 {
-    static const int off = [] { const char *e = getenv("DM4D_GN_SLAB"); return e && atoi(e) == 0 ? 1 : 0; }();      // (A/B switch)
-    if (off) return false;
     const int cpg = a.C / a.G;
     int g = 8, x = cpg;                 // gb = 8 / gcd(cpg, 8)
     while (x % 2 == 0 && g > 1) { x /= 2; g /= 2; }
@@ -355,10 +352,10 @@ static bool gn_slab_plan(const GnArgs &a, int &gb, int &ppp, int &threads)
     threads = kSlabThreads / ppp * ppp;
     if (gb * cpg > threads) return false;                                       // (the channel -> group stage has a lane per channel)
     const int R = threads / ppp;
-    // measured per shape (tools/gn_shapes.py): 1.4-2.9x faster than the two launches at <= 16 x 16 pixels per sample (7-9 us against
+    // measured per shape (profiles/r03_zero123.md): 1.4-2.9x faster than the two launches at <= 16 x 16 pixels per sample (7-9 us against
     // 10-23), 10 % slower at 32 x 32 (8 samples x 8 group blocks = 64 workgroups of 20 pieces per thread) and at the VAE's 64 x 64
-    static const int max_hw = [] { const char *e = getenv("DM4D_GN_SLAB_MAX_HW"); return e ? atoi(e) : 256; }();      // (A/B switch)
-    return a.HW <= max_hw && (a.HW + R - 1) / R <= kSlabPPT;
+    constexpr int kSlabMaxHW = 256;
+    return a.HW <= kSlabMaxHW && (a.HW + R - 1) / R <= kSlabPPT;
 }
 
 static size_t gn_lds_bytes(int C, int G, int vec, bool stats)

@@ -1,28 +1,17 @@
 // nodenet.hip -- the deformation network of the graph nodes as ONE operator: HexPlane query + MLP forward in one launch,
-// their backward in three (the separate operators of hexplane.hip / deform_mlp.hip take 2 and 5, with a torch kernel for
+// their backward in two (the separate operators of hexplane.hip / deform_mlp.hip take 2 and 5, with a torch kernel for
 // 2 t - 1 in front).  Same kernels' bodies, regrouped:
 //
 //   forward   k_nodenet_fwd   workgroup = 16 (frame, node) rows: the 16 x 128 feature tile is computed straight into the LDS
 //                              tile the MLP's first layer reads (and written once to HBM for the backward), then the MLP
-//   backward  k_mlp_bwd       dy_k, dx, dh, d feat                                                         (deform_mlp.hip)
-//             k_nodenet_bwd2  independent jobs side by side: per-point plane-product gradients | parameter-gradient tiles of
-//                              the MLP (split-K partials) | zero fill of the time planes
-//             k_nodenet_bwd3  time-plane columns | spatial texels | reduction of the MLP partials
+//   backward  k_nodenet_bwdA  MLP backward | zero fill of the time planes | ticket reset             (details below)
+//             k_nodenet_bwdB  parameter-gradient tiles | time-plane columns | spatial texels
 // Every step of the per-iteration chain is latency-bound at 4000 rows ("the step is the sum of its
-// chain"): what this buys is four launches and two dependent round trips, not bandwidth.
+// chain"): what this buys is launches and dependent round trips, not bandwidth.
 //
 // Reference: C/geometry/deformation.py:88-305,430-436 queried by C/geometry/dynamic_sugar.py:420-431.
-#include <stdlib.h>
-
 #include "hexplane.hip"
 #include "deform_mlp.hip"
-
-// Probe builds (tools/build_variant.sh <name> "-DDM4D_PROBE_NODENET=n" nodenet.hip; never the product): 1 = no plane sampling (constant
-// features), 2 = no MLP, 3 = no [in][out] weight copies, 4 / 5 / 6 = bwd3 without its time columns / spatial texels / split-K reduction,
-// 7 / 8 / 9 = bwd2 without its parameter-gradient tiles / per-point products / zero fill: what each phase of the four launches costs.
-#ifndef DM4D_PROBE_NODENET
-#define DM4D_PROBE_NODENET 0
-#endif
 
 namespace dm4d {
 
@@ -43,26 +32,24 @@ __global__ __launch_bounds__(kNodeFwdThreads) void k_nodenet_fwd(HexDesc hd, Mlp
     for (int e = tid; e < kRT * IN; e += kNodeFwdThreads) {
         const int r = e / IN, col = e % IN, row = row0 + r;
         float v = 0.f;
-        if (DM4D_PROBE_NODENET == 1) v = 1.0f + 1e-3f * (float)col;
-        else if (row < d.P) v = hex_feature(hd, nodes, times, row / hd.M, row % hd.M, col / kHexCh, col % kHexCh, feat, samples);
+        if (row < d.P) v = hex_feature(hd, nodes, times, row / hd.M, row % hd.M, col / kHexCh, col % kHexCh, feat, samples);
         sf[((col >> 2) * kXs + r) * 4 + (col & 3)] = v;
     }
-    if (DM4D_PROBE_NODENET == 2) return;
-    if (DM4D_PROBE_NODENET == 3) d.W0T = nullptr;
     if (tid >= 256) { __syncthreads(); return; }        // (their share of the barrier inside mlp_fwd_block that publishes s_f)
     mlp_fwd_block(d, (int)blockIdx.x, (int)gridDim.x, s_f, Hs, Ys, out0, out1, out2, out3);
 }
 
-struct NodeBwdJobs { unsigned point_blocks, wgrad_tiles, wgrad_blocks, zero_blocks, plane_blocks, reduce_blocks, mlp_blocks; };
+struct NodeBwdJobs { unsigned wgrad_tiles, wgrad_blocks, zero_blocks, mlp_blocks; };
 
-// ---- round 5: the backward as TWO launches (the three below stay: DM4D_NODENET_BWD3=1, the A/B switch) ----
+// ---- round 5: the backward as TWO launches (rounds 3-4 took three: k_mlp_bwd, then the parameter-gradient tiles, per-point products and zero
+//      fill, then the time columns, spatial texels and split-K reduction) ----
 //   k_nodenet_bwdA   MLP backward of 16 rows (dy_k, dx, dh) whose dL/dfeat tile goes straight on to the HexPlane's per-point
 //                    plane-product gradients G (the lane that holds four consecutive channels of a row reads its six saved samples as
 //                    float4s and rewrites them in place: hex_bwd_point's products in its order) | zero fill of the time planes | the
 //                    parameter-gradient tiles' arrival tickets cleared
 //   k_nodenet_bwdB   parameter-gradient tiles with the row-slice reduction inside the launch (mlp_wgrad_block's last-arriving slice) |
 //                    time-plane columns | spatial texels
-// Measured on the bench scene (tools/build_variant.sh probes, profiles/r05_nodenet_probe.txt): of the 67 us of k_mlp_bwd (12) ->
+// Measured on the bench scene (round 5 timing builds, profiles/r05_nodenet_probe.txt): of the 67 us of k_mlp_bwd (12) ->
 // bwd2 (21) -> bwd3 (34) the per-point products and the split-K reduction cost ~4 and ~0 us of kernel time but each holds a launch
 // boundary and a dependent round trip on the step's serial chain; bwd3's 34 us are its two gathers (9 + 11) on a ~14 us floor.
 struct PointGrad {
@@ -121,35 +108,6 @@ __global__ __launch_bounds__(256) void k_nodenet_bwdB(HexDesc hd, MlpDesc d, Nod
     }
     b -= (unsigned)pl.n_time;
     hex_bwd_spatial(hd, b, nodes, pl.n_spatial, pl.sp_scale, pl.sp_plane, pl.sp_texel, pl.sp_off, pl.sp_item, G, hg);
-}
-
-__global__ __launch_bounds__(256) void k_nodenet_bwd2(HexDesc hd, MlpDesc d, NodeBwdJobs jb, const float *__restrict__ g_feat, float *__restrict__ G,
-                                                      HexGrads hg, const float *__restrict__ feat, const float *__restrict__ Hs,
-                                                      const float *__restrict__ Ys, const float *g0, const float *g1, const float *g2,
-                                                      const float *g3)
-{
-    unsigned b = blockIdx.x;
-    if (b < jb.wgrad_blocks) { if (DM4D_PROBE_NODENET != 7) mlp_wgrad_block(d, (int)(b % jb.wgrad_tiles), (int)(b / jb.wgrad_tiles), feat, Hs, Ys, g0, g1, g2, g3); return; }
-    b -= jb.wgrad_blocks;
-    if (b < jb.point_blocks) { if (DM4D_PROBE_NODENET != 8) hex_bwd_point(hd, b, g_feat, G); return; }
-    if (DM4D_PROBE_NODENET != 9) hex_zero(hg, b - jb.point_blocks);
-}
-
-__global__ __launch_bounds__(256) void k_nodenet_bwd3(HexDesc hd, MlpDesc d, NodeBwdJobs jb, const float *__restrict__ nodes,
-                                                      const float *__restrict__ times, HexPlan pl, const float *__restrict__ G, HexGrads hg,
-                                                      MlpGrads mg)
-{
-    unsigned b = blockIdx.x;
-    if (b < (unsigned)pl.n_time) {
-        if (DM4D_PROBE_NODENET != 4) hex_bwd_time(hd, b, nodes, times, pl.n_time, pl.tp_scale, pl.tp_plane, pl.tp_col, pl.tp_off, pl.tp_item, G, hg);
-        return;
-    }
-    b -= (unsigned)pl.n_time;
-    if (b < jb.plane_blocks) {
-        if (DM4D_PROBE_NODENET != 5) hex_bwd_spatial(hd, b, nodes, pl.n_spatial, pl.sp_scale, pl.sp_plane, pl.sp_texel, pl.sp_off, pl.sp_item, G, hg);
-        return;
-    }
-    if (DM4D_PROBE_NODENET != 6) mlp_reduce_block(d, mg, kKSplit, b - jb.plane_blocks);
 }
 
 }  // namespace dm4d
@@ -235,49 +193,25 @@ int dm4d_nodenet_backward(int32_t S, int32_t M, int32_t B, const int32_t *res, c
     if (flags & DM4D_HEX_KEEP_SPATIAL)
         for (int s = 0; s < S; ++s)
             for (int p : {0, 1, 3}) hg.keep_mask |= 1ull << (s * kHexPlanes + p);
-    static const bool three_launches = getenv("DM4D_NODENET_BWD3") && atoi(getenv("DM4D_NODENET_BWD3")) != 0;      // (A/B switch: rounds 3-4's chain)
-    if (!three_launches) {
-        NodeBwdJobs jb;
-        memset(&jb, 0, sizeof(jb));
-        jb.mlp_blocks = (unsigned)((P + kRT - 1) / kRT);
-        jb.zero_blocks = kHexZeroBlocks * (unsigned)hg.n;
-        jb.wgrad_tiles = (unsigned)(4 * (d.IN / 16 + 1) + 25 * d.n_heads);
-        jb.wgrad_blocks = jb.wgrad_tiles * kKSplit;
-        jb.plane_blocks = (unsigned)(((size_t)(n_spatial > 0 ? n_spatial : 0) * kHexCh + 255) / 256);
-        if ((int)jb.wgrad_tiles > kMaxTickets) { set_error("nodenet: %u parameter-gradient tiles", jb.wgrad_tiles); return DM4D_ERR_UNSUPPORTED; }
-        hipLaunchKernelGGL(k_nodenet_bwdA, dim3(jb.mlp_blocks + jb.zero_blocks + 1), dim3(256), 0, st, hd, d, jb, (float *)samples, hg, h_save,
-                           g[0], g[1], g[2], g[3]);
-        DM4D_HIP_CHECK(hipGetLastError());
-        HexPlan pl = {n_spatial, n_time < 0 ? 0 : n_time, sp_scale, sp_plane, sp_texel, sp_off, sp_item, tp_scale, tp_plane, tp_col, tp_off, tp_item};
-        hipLaunchKernelGGL(k_nodenet_bwdB, dim3(jb.wgrad_blocks + (unsigned)pl.n_time + jb.plane_blocks), dim3(256), 0, st, hd, d, jb, nodes, times,
-                           pl, (const float *)samples, hg, mg, feat, h_save, y_save, g[0], g[1], g[2], g[3]);
-        DM4D_HIP_CHECK(hipGetLastError());
-        if (!DM4D_WGRAD_FINISH) {
-            const size_t np = partial_floats(d);
-            hipLaunchKernelGGL(k_mlp_reduce, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, d, mg, kKSplit);
-            DM4D_HIP_CHECK(hipGetLastError());
-        }
-        return DM4D_OK;
-    }
-    // 1: dL/dy_k, dL/dh, dL/dfeat
-    hipLaunchKernelGGL(k_mlp_bwd, dim3((P + kRT - 1) / kRT), dim3(256), 0, st, d, h_save, g[0], g[1], g[2], g[3], g_feat);
-    DM4D_HIP_CHECK(hipGetLastError());
-    // 2: MLP parameter-gradient tiles | per-point plane products | zero fill
     NodeBwdJobs jb;
+    jb.mlp_blocks = (unsigned)((P + kRT - 1) / kRT);
+    jb.zero_blocks = kHexZeroBlocks * (unsigned)hg.n;
     jb.wgrad_tiles = (unsigned)(4 * (d.IN / 16 + 1) + 25 * d.n_heads);
     jb.wgrad_blocks = jb.wgrad_tiles * kKSplit;
-    jb.point_blocks = (unsigned)(((size_t)B * M * S * kHexCh + 255) / 256);
-    jb.zero_blocks = kHexZeroBlocks * (unsigned)hg.n;
-    jb.plane_blocks = (unsigned)(((size_t)(n_spatial > 0 ? n_spatial : 0) * kHexCh + 255) / 256);
-    jb.reduce_blocks = (unsigned)((partial_floats(d) + 255) / 256);
-    hipLaunchKernelGGL(k_nodenet_bwd2, dim3(jb.wgrad_blocks + jb.point_blocks + jb.zero_blocks), dim3(256), 0, st, hd, d, jb, g_feat,
-                       (float *)samples, hg, feat, h_save, y_save, g[0], g[1], g[2], g[3]);
+    const unsigned plane_blocks = (unsigned)(((size_t)(n_spatial > 0 ? n_spatial : 0) * kHexCh + 255) / 256);
+    if ((int)jb.wgrad_tiles > kMaxTickets) { set_error("nodenet: %u parameter-gradient tiles", jb.wgrad_tiles); return DM4D_ERR_UNSUPPORTED; }
+    hipLaunchKernelGGL(k_nodenet_bwdA, dim3(jb.mlp_blocks + jb.zero_blocks + 1), dim3(256), 0, st, hd, d, jb, (float *)samples, hg, h_save,
+                       g[0], g[1], g[2], g[3]);
     DM4D_HIP_CHECK(hipGetLastError());
-    // 3: the planes' gathers | the reduction of the MLP partials
     HexPlan pl = {n_spatial, n_time < 0 ? 0 : n_time, sp_scale, sp_plane, sp_texel, sp_off, sp_item, tp_scale, tp_plane, tp_col, tp_off, tp_item};
-    hipLaunchKernelGGL(k_nodenet_bwd3, dim3((unsigned)pl.n_time + jb.plane_blocks + jb.reduce_blocks), dim3(256), 0, st, hd, d, jb, nodes, times,
-                       pl, (const float *)samples, hg, mg);
+    hipLaunchKernelGGL(k_nodenet_bwdB, dim3(jb.wgrad_blocks + (unsigned)pl.n_time + plane_blocks), dim3(256), 0, st, hd, d, jb, nodes, times,
+                       pl, (const float *)samples, hg, mg, feat, h_save, y_save, g[0], g[1], g[2], g[3]);
     DM4D_HIP_CHECK(hipGetLastError());
+    if (!DM4D_WGRAD_FINISH) {
+        const size_t np = partial_floats(d);
+        hipLaunchKernelGGL(k_mlp_reduce, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, d, mg, kKSplit);
+        DM4D_HIP_CHECK(hipGetLastError());
+    }
     return DM4D_OK;
 }
 

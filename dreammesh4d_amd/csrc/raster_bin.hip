@@ -666,11 +666,10 @@ AuxStream *aux_stream()
     return &a;
 }
 
-// workgroups of the large variant's launch: one per CU (DM4D_SORT_LARGE_GRID overrides: the A/B switch; 0 = one per block, as rounds 1-5)
+// workgroups of the large variant's launch: one per CU (rounds 1-5 launched one per block)
 static unsigned large_grid_cap()
 {
     static const unsigned cap = [] {
-        if (const char *e = getenv("DM4D_SORT_LARGE_GRID")) { const long v = atol(e); return v <= 0 ? 0xFFFFFFFFu : (unsigned)v; }
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         return (unsigned)max(cus, 1);

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One more build of libdm4d_hip.so beside the tree's: tools/build_variant.sh <name> "<extra hipcc flags>" <file.hip> [file.hip ...]
-# recompiles the named translation units with the extra flags (probe switches, -D...), links them with the tree's other objects
+# recompiles the named translation units with the extra flags (-D of the #ifndef tuning constants ...), links them with the tree's other objects
 # -> build_ab/<name>.so (git-ignored; travels to the GPU box) for tools/ab_many.sh / ab_kernels.sh / prof_two_libs.sh.
 set -e
 REPO=$(cd "$(dirname "$0")/.." && pwd)
