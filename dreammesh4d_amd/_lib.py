@@ -148,6 +148,8 @@ _SIGNATURES = {
     "dm4d_debug_trace": (C.c_int, [vp, C.c_uint32]),
     "dm4d_debug_sort_trace": (C.c_int, [vp]),
     "dm4d_mark_visible": (C.c_int, [C.c_int32, vp, vp, vp, vp]),
+    "dm4d_sh_eval_forward": (C.c_int, [C.c_int32] * 3 + [vp] * 6),
+    "dm4d_sh_eval_backward": (C.c_int, [C.c_int32] * 3 + [vp] * 8),
     "dm4d_groupnorm_nhwc_forward": (C.c_int, [C.c_int32] * 5 + [vp, vp, C.c_int32, vp, vp, C.c_float, C.c_int32, vp, vp, vp, C.c_int32, vp]),
     "dm4d_groupnorm_nhwc_backward": (C.c_int, [C.c_int32] * 5 + [vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp]),
     "dm4d_sds_prepare": (C.c_int, [C.c_int32] * 3 + [C.c_float] + [vp] * 17),

@@ -41,6 +41,20 @@ ProfScope::~ProfScope()
     (void)hipEventRecord(g_prof_pairs[(size_t)(uintptr_t)slot - 1].b, st);
 }
 
+// degree 0..3 with at least (degree + 1)^2 stored coefficients
+static int check_sh(int degree, int sh_coeffs)
+{
+    if (degree < 0 || degree > 3) {
+        set_error("sh_degree %d with %d coefficients is not supported (degrees 0 to 3 are)", degree, sh_coeffs);
+        return DM4D_ERR_UNSUPPORTED;
+    }
+    if (sh_coeffs < (degree + 1) * (degree + 1)) {
+        set_error("sh_degree %d needs %d coefficients, shs has %d", degree, (degree + 1) * (degree + 1), sh_coeffs);
+        return DM4D_ERR_INVALID;
+    }
+    return DM4D_OK;
+}
+
 static int check_settings(const dm4d_raster_settings *s, const dm4d_raster_inputs *in)
 {
     if (!s || !in) { set_error("null settings/inputs"); return DM4D_ERR_INVALID; }
@@ -67,10 +81,17 @@ static int check_settings(const dm4d_raster_settings *s, const dm4d_raster_input
             set_error("n_channels must be 3 or 6 (got %d)", in->n_channels);
             return DM4D_ERR_INVALID;
         }
-        if (in->n_channels == 6 && in->shs) { set_error("6 channels need colors_precomp"); return DM4D_ERR_INVALID; }
-        if (in->shs && (s->sh_degree != 0 || in->sh_coeffs < 1)) {
-            set_error("sh_degree %d with %d coefficients is not supported (only degree 0)", s->sh_degree, in->sh_coeffs);
-            return DM4D_ERR_UNSUPPORTED;
+        if (in->n_channels == 6 && in->shs) {
+            set_error("6 channels need colors_precomp (got shs with sh_degree %d, %d coefficients)", s->sh_degree, in->sh_coeffs);
+            return DM4D_ERR_INVALID;
+        }
+        if (in->shs) {
+            const int rc = check_sh(s->sh_degree, in->sh_coeffs);
+            if (rc) return rc;
+            if (s->sh_degree > 0 && !s->campos) {
+                set_error("sh_degree %d needs campos (a device pointer)", s->sh_degree);
+                return DM4D_ERR_INVALID;
+            }
         }
     }
     return DM4D_OK;
@@ -170,6 +191,13 @@ int dm4d_rasterize_prepare(const dm4d_raster_settings *s, const dm4d_raster_inpu
     DM4D_HIP_CHECK(hipMemsetAsync((char *)geom + L.zero_begin, 0, L.zero_bytes, st));
     rc = launch_preprocess(d, st);
     if (rc) return rc;
+    if (in->shs && s->sh_degree > 0) {
+        // k_preprocess has written the degree-0 colour; the view-dependent one replaces it (a launch of its own: the
+        // degree-0 kernels stay as they are)
+        const GeomPtrs g = geom_ptrs(geom, L);
+        rc = launch_sh_eval_forward(in->N, s->sh_degree, in->sh_coeffs, in->means3D, s->campos, in->shs, g.rgb, g.clamped, st);
+        if (rc) return rc;
+    }
     return launch_colscan(d, st);
 }
 
@@ -247,6 +275,11 @@ int dm4d_rasterize_backward(const dm4d_raster_settings *s, const dm4d_raster_inp
     if (rc) return rc;
     if (!geom || !binning || !image || !grad || !dL_dcolor) { set_error("null workspace/grad input"); return DM4D_ERR_INVALID; }
     if (in->N > 0 && (!dL_dmeans2D || !dL_dmeans3D || !radii)) { set_error("dL_dmeans2D/dL_dmeans3D/radii required"); return DM4D_ERR_INVALID; }
+    const bool sh_hi = in->N > 0 && in->shs && s->sh_degree > 0;
+    if (sh_hi && (!dL_dcolors || !dL_dsh)) {
+        set_error("sh_degree %d: dL_dcolors [N,3] (receives dL/drgb) and dL_dsh [N,%d,3] are required", s->sh_degree, in->sh_coeffs);
+        return DM4D_ERR_INVALID;
+    }
     hipStream_t st = (hipStream_t)stream;
     BatchDesc d = single_view_batch(s, in);
     d.radii = const_cast<int32_t *>(radii);
@@ -260,10 +293,16 @@ int dm4d_rasterize_backward(const dm4d_raster_settings *s, const dm4d_raster_inp
     d.dLq = (float *)grad;
     if (record_capacity < 0 || record_capacity > 0xFFFFFFF0ll) { set_error("record_capacity out of range"); return DM4D_ERR_INVALID; }
     d.rec_cap = (uint32_t)record_capacity;
-    d.o = BwdOutputs{dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dcolors, dL_dsh, dL_dscales, dL_drotations, dL_dcov3D};
+    // sh_degree > 0: the gather leaves dL_dsh alone and writes dL/drgb to dL_dcolors, from which the SH backward fills dL_dsh
+    // and adds the direction term to dL_dmeans3D
+    d.o = BwdOutputs{dL_dmeans2D, dL_dmeans3D, dL_dopacity, dL_dcolors, sh_hi ? nullptr : dL_dsh, dL_dscales, dL_drotations, dL_dcov3D};
     rc = launch_render_bwd(d, st);
     if (rc) return rc;
-    return launch_gather_bwd(d, st);
+    rc = launch_gather_bwd(d, st);
+    if (rc || !sh_hi) return rc;
+    const GeomPtrs g = geom_ptrs(const_cast<void *>(geom), geom_layout(in->N, s->image_height, s->image_width));
+    return launch_sh_eval_backward(in->N, s->sh_degree, in->sh_coeffs, in->means3D, s->campos, in->shs, g.clamped, radii, dL_dcolors,
+                                   dL_dsh, dL_dmeans3D, 1, st);
 }
 
 int64_t dm4d_rasterize_forward(const dm4d_raster_settings *s, const dm4d_raster_inputs *in, float *out_color,
@@ -353,6 +392,30 @@ int dm4d_mark_visible(int32_t N, const float *means3D, const float *viewmatrix, 
 {
     if (N < 0 || (N > 0 && (!means3D || !viewmatrix || !present))) { set_error("bad arguments"); return DM4D_ERR_INVALID; }
     return launch_mark_visible(N, means3D, viewmatrix, present, (hipStream_t)stream);
+}
+
+int dm4d_sh_eval_forward(int32_t N, int32_t degree, int32_t M, const float *means3D, const float *campos, const float *shs,
+                         float *rgb, uint8_t *clamped, dm4d_stream_t stream)
+{
+    if (N < 0) { set_error("negative N"); return DM4D_ERR_INVALID; }
+    const int rc = check_sh(degree, M);
+    if (rc) return rc;
+    if (N > 0 && (!means3D || !campos || !shs || !rgb || !clamped)) { set_error("dm4d_sh_eval_forward: null argument"); return DM4D_ERR_INVALID; }
+    return launch_sh_eval_forward(N, degree, M, means3D, campos, shs, rgb, clamped, (hipStream_t)stream);
+}
+
+int dm4d_sh_eval_backward(int32_t N, int32_t degree, int32_t M, const float *means3D, const float *campos, const float *shs,
+                          const uint8_t *clamped, const float *dL_drgb, float *dL_dsh, float *dL_dmeans3D, dm4d_stream_t stream)
+{
+    if (N < 0) { set_error("negative N"); return DM4D_ERR_INVALID; }
+    const int rc = check_sh(degree, M);
+    if (rc) return rc;
+    if (N > 0 && (!means3D || !campos || !shs || !clamped || !dL_drgb || !dL_dsh || !dL_dmeans3D)) {
+        set_error("dm4d_sh_eval_backward: null argument");
+        return DM4D_ERR_INVALID;
+    }
+    return launch_sh_eval_backward(N, degree, M, means3D, campos, shs, clamped, nullptr, dL_drgb, dL_dsh, dL_dmeans3D, 0,
+                                   (hipStream_t)stream);
 }
 
 }  // extern "C"

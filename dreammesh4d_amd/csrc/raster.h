@@ -467,5 +467,12 @@ int launch_n_contrib_tile_positions(void *geom, void *binning, void *image, int 
 int set_trace_buffer(void *dev_ptr, uint32_t min_work);
 int set_sort_trace_buffer(void *dev_ptr);
 int launch_mark_visible(int N, const float *means3D, const float *view, uint8_t *present, hipStream_t st);
+// sh_eval.hip: colour from spherical harmonics of degree 0..3 (M stored coefficients per Gaussian) and its backward.
+// radii (optional): rows with radius 0 get zero gradients; accumulate: add to dL_dmeans3D instead of writing it
+int launch_sh_eval_forward(int N, int degree, int M, const float *means3D, const float *campos, const float *shs, float *rgb,
+                           uint8_t *clamped, hipStream_t st);
+int launch_sh_eval_backward(int N, int degree, int M, const float *means3D, const float *campos, const float *shs,
+                            const uint8_t *clamped, const int32_t *radii, const float *dL_drgb, float *dL_dsh, float *dL_dmeans3D,
+                            int accumulate, hipStream_t st);
 
 }  // namespace dm4d

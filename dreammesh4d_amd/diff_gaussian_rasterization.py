@@ -8,6 +8,10 @@ and calls at ...temporal.py:129-144 (settings), :169-178 (RGB pass), :202-211 (n
 Same names, argument meaning and error behaviour; the compute is libdm4d_hip.so
 (hand-written HIP for gfx950) through the C ABI of include/dm4d.h.  No CPU fallback.
 
+``shs`` [N,M,3] with ``sh_degree`` 0 to 3 (M >= (sh_degree + 1)^2) is evaluated in the library (csrc/sh_eval.hip for degree > 0:
+view-dependent colour from ``campos``); autograd returns every coefficient's gradient and, for degree > 0, the direction term
+inside the gradient of ``means3D``.
+
 ``dreammesh4d_amd.install_compat()`` registers this module under the upstream name so the
 reference's renderer files import it unmodified.
 """

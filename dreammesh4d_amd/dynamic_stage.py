@@ -31,6 +31,7 @@ import torch.nn.functional as F
 
 from . import distributed as D
 from . import synthetic as syn
+from .geometry import reject_sh_coefficients
 from .schedule import C
 from .loss_sum import weighted_sum
 from .views import render_views
@@ -87,6 +88,10 @@ class DynamicStage:
                  normal_consistency=None, arap=None, milestone_arap_reg=100, inter_frame_reg=0, num_inter_frames=10,
                  length_inter_frames=0.1, sharded_optimizer=None, lambdas=None, optimizer_hyper=None, ref_depths=None, ref_normals=None,
                  laplacian_smoothing=None):
+        if int(static.get("sh_levels", 1)) > 1:
+            raise NotImplementedError(f"DynamicStage: sh_levels = {int(static['sh_levels'])} (view-dependent colour) is not implemented: "
+                                      "the step object blends one colour array in every view and needs sh_levels = 1")
+        reject_sh_coefficients(static.get("rgb"), "DynamicStage")
         self.r, self.net, self.nodes, self.static = renderer, net, nodes, static
         # loss weights: `system.loss` of the configuration (from_cfg), defaulting to the shipped sugar_dynamic_dg.yaml values
         self.lam = dict(LAMBDA)

@@ -11,6 +11,7 @@ per-view work is in the HIP kernels (ops.py / rasterizer).
   strengths            geometry/sugar.py:470-472
   quaternions          geometry/sugar.py:489-518  (pytorch3d matrix_to_quaternion restated)
   points_rgb           geometry/sugar.py:640-661  (sh_levels == 1), gaussian_base.py:30-40 (SH2RGB)
+  points_rgb_sh        geometry/sugar.py:640-661  (sh_levels 2..4: view-dependent, the HIP kernels of csrc/sh_eval.hip)
   face_normals         geometry/sugar.py:520-526
 """
 import torch
@@ -74,6 +75,80 @@ def strengths(densities):
 
 def points_rgb(sh_dc):
     return SH2RGB(sh_dc).view(-1, 3)
+
+
+class _PointsRgbSH(torch.autograd.Function):
+    """max(sum_k B_k(normalize(points - campos)) sh[:, k] + 0.5, 0) for the first (degree + 1)^2 coefficients:
+    dm4d_sh_eval_forward / dm4d_sh_eval_backward (include/dm4d.h).  HIP device only."""
+
+    @staticmethod
+    def forward(ctx, sh, points, campos, degree):
+        from . import _lib
+
+        L = _lib.lib()
+        dev = points.device
+        if dev.type != "cuda":
+            raise RuntimeError("points_rgb_sh: tensors must live on a HIP device; there is no CPU path")
+        c = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        sh, points, campos = c(sh), c(points), c(campos).reshape(3)
+        N, M = int(sh.shape[0]), int(sh.shape[1])
+        rgb = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        clamped = torch.empty(N, 3, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.dm4d_sh_eval_forward(N, int(degree), M, points.data_ptr(), campos.data_ptr(), sh.data_ptr(), rgb.data_ptr(),
+                                              clamped.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "dm4d_sh_eval_forward")
+        ctx.save_for_backward(sh, points, campos, clamped)
+        ctx.degree = int(degree)
+        return rgb
+
+    @staticmethod
+    def backward(ctx, g_rgb):
+        from . import _lib
+
+        L = _lib.lib()
+        sh, points, campos, clamped = ctx.saved_tensors
+        dev = points.device
+        N, M = int(sh.shape[0]), int(sh.shape[1])
+        g_rgb = g_rgb.detach().to(torch.float32).contiguous()
+        d_sh, d_pts = torch.empty_like(sh), torch.empty_like(points)
+        with torch.cuda.device(dev):
+            _lib.check(L.dm4d_sh_eval_backward(N, ctx.degree, M, points.data_ptr(), campos.data_ptr(), sh.data_ptr(), clamped.data_ptr(),
+                                               g_rgb.data_ptr(), d_sh.data_ptr(), d_pts.data_ptr(),
+                                               torch.cuda.current_stream(dev).cuda_stream), "dm4d_sh_eval_backward")
+        return d_sh, d_pts, None, None
+
+
+def points_rgb_sh(sh, points, camera_centers, sh_levels):
+    """``SuGaRModel.get_points_rgb`` (sugar.py:640-661) for `sh` [N, >= sh_levels^2, 3] seen from ONE camera centre ([3] or
+    [1,3]): the clamped view-dependent colour [N,3].  ``sh_levels == 1`` is ``points_rgb`` of the DC term (not clamped, as there)."""
+    sh_levels = int(sh_levels)
+    if sh_levels == 1:
+        return points_rgb(sh[:, :1])
+    if not 2 <= sh_levels <= 4:
+        raise ValueError(f"sh_levels must be 1 to 4 (got {sh_levels})")
+    if camera_centers is None:
+        raise ValueError("camera_centers must be provided.")
+    if camera_centers.numel() != 3:
+        raise NotImplementedError(f"points_rgb_sh: one camera centre per call (got shape {tuple(camera_centers.shape)}); "
+                                  "sh_levels > 1 has no per-point or batched form here")
+    return _PointsRgbSH.apply(sh, points, camera_centers, sh_levels - 1)
+
+
+def require_sh_levels_1(geometry, what):
+    """The batched paths (views / gviews / the step object / the stages / the texture bake) take ONE colour array for all their
+    views: they refuse a geometry with view-dependent colour instead of rendering its DC term."""
+    n = int(getattr(geometry, "sh_levels", 1))
+    if n > 1:
+        raise NotImplementedError(f"{what}: sh_levels = {n} (view-dependent colour) is only implemented on the single-view paths "
+                                  "(the rasterizer operator with shs / sh_degree, geometry.points_rgb_sh); this path blends one "
+                                  "colour array in every view and needs sh_levels = 1")
+
+
+def reject_sh_coefficients(colors, what):
+    """Same refusal for the entry points that see tensors only: SH coefficients [N,M,3] where a colour array [N,C] is expected."""
+    if colors is not None and colors.dim() == 3:
+        raise NotImplementedError(f"{what}: got SH coefficients of shape {tuple(colors.shape)}; sh_levels > 1 (sh_degree > 0) is not "
+                                  "implemented on the batched paths, which take one colour array [N,C] for all views")
 
 
 def face_normals(verts, faces, fv=None):

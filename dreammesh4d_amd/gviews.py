@@ -13,6 +13,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .geometry import reject_sh_coefficients
 from .views import ViewRenderer, _f32, _p
 
 
@@ -122,6 +123,7 @@ def render_gaussian_views(renderer: GaussianViews, means3D, rotations, scales, o
     RGB | normal) from the cameras viewmats / projmats [B,4,4] (row-vector convention, as the rasterizer settings hold them).
     Returns dict: color [B,6,H,W], depth [B,1,H,W], alpha [B,1,H,W], radii [B,N] int32.  means2D [B,N,3] (optional, zeros with
     requires_grad): the screen-space gradient carrier (``viewspace_points``) of every view."""
+    reject_sh_coefficients(colors6, "render_gaussian_views")
     args = (renderer, means3D, rotations, scales, opacities, colors6, viewmats, projmats, bg6, means2D)
     color, depth, alpha, radii = _RenderGaussianViews.apply(*args)
     if not renderer.calibrated:

@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from . import views
+from .geometry import points_rgb_sh, require_sh_levels_1
 
 
 # ------------------------------------------------------------------------------------------------ camera
@@ -170,6 +171,7 @@ class DiffGaussianTemporal:
 
     def batch_forward(self, batch: Dict) -> Dict:
         g = self.geometry
+        require_sh_levels_1(g, "DiffSuGaR.batch_forward")
         B = int(batch["c2w"].shape[0])
         H, W = int(batch["height"]), int(batch["width"])
         w2c, full, _, fovy = batch_cameras(batch, g.device)
@@ -210,6 +212,7 @@ class DiffGaussianTemporal:
         from .texture_export import canonical_gaussians
 
         g = self.geometry
+        require_sh_levels_1(g, "DiffSuGaR.render_canonical")
         key = ("canonical", int(H), int(W), round(float(tanfov), 9))
         if key not in self._renderers:
             self._renderers[key] = gviews.GaussianViews(g.n_gaussians, H, W, tanfov, g.device)
@@ -253,7 +256,7 @@ class DiffGaussianTemporal:
         vsp = torch.zeros(g.n_gaussians, 3, device=g.device, requires_grad=True)
         scales = g.timed_scales(ds, do) if g.d_scale else g.get_scaling      # per frame under d_scale (dynamic_sugar.py:717-720)
         out = views.render_views(r, dx, dr, ds, do, g.static_quaternions, scales, g.get_opacity.reshape(-1),
-                                 g.get_points_rgb(), viewpoint_camera.world_view_transform[None],
+                                 g.get_points_rgb(viewpoint_camera.camera_center), viewpoint_camera.world_view_transform[None],
                                  viewpoint_camera.full_proj_transform[None], torch.cat([bg, bg]),
                                  frame_index=frame_index, means2D=vsp[None])
         color, depth, alpha = out["color"][0], out["depth"][0], out["alpha"][0]
@@ -321,6 +324,9 @@ class DiffSuGaRNormal:
         means3D = ga["xyz"]
         vsp = torch.zeros_like(means3D, requires_grad=True)
         rgb = ga["rgb"] if override_color is None else override_color
+        if override_color is None and getattr(g, "sh_levels", 1) > 1:
+            # view-dependent colour (sugar.py:640-661) of this view's camera centre; clamped like the rasterizer's own evaluation
+            rgb = points_rgb_sh(g.get_features, means3D, viewpoint_camera.camera_center, g.sh_levels)
         rs = dgr.GaussianRasterizationSettings(
             image_height=H, image_width=W, tanfovx=math.tan(0.5 * float(viewpoint_camera.FoVx)),
             tanfovy=math.tan(0.5 * float(viewpoint_camera.FoVy)), bg=torch.cat([bg, bg]), scale_modifier=scaling_modifier,

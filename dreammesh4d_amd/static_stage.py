@@ -19,6 +19,7 @@ import torch.nn.functional as F
 
 from . import distributed as D
 from . import synthetic as syn
+from .geometry import require_sh_levels_1
 from .loss_sum import weighted_sum
 from .schedule import C
 
@@ -39,6 +40,7 @@ def tv_loss(x):
 class StaticStage:
     def __init__(self, geometry, renderer, ref_image, ref_mask, H, W, guidance=None, random_views=4, normal_consistency=None,
                  laplacian_smoothing=None, seed=0, lambdas=None, message_adamw=None):
+        require_sh_levels_1(geometry, "StaticStage")
         self.g, self.r = geometry, renderer
         self.lam = dict(LAMBDA)            # `system.loss` of the configuration (from_cfg); defaults: sugar_static_refine.yaml
         self.lam.update(lambdas or {})

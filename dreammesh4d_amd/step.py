@@ -27,6 +27,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .geometry import reject_sh_coefficients
 from . import hexplane as hx
 
 
@@ -74,6 +75,7 @@ class DynamicStep:
         from .deformation import DeformationNetwork
 
         assert isinstance(net, DeformationNetwork)
+        reject_sh_coefficients(rgb, "DynamicStep")
         self.r, self.net = renderer, net
         self.dev = renderer.device
         self.B = int(n_views)

@@ -90,11 +90,18 @@ def RGB2SH(rgb):
     return (rgb - 0.5) / 0.28209479177387814
 
 
+def _check_sh_levels(sh_levels):
+    """``sh_levels`` of SuGaRModel.Config (sugar.py:37): 1 (DC only) to 4 (degree 3)."""
+    if int(sh_levels) != sh_levels or not 1 <= int(sh_levels) <= 4:
+        raise ValueError(f"sh_levels must be 1, 2, 3 or 4 (got {sh_levels!r})")
+    return int(sh_levels)
+
+
 class DynamicSuGaR(nn.Module):
     def __init__(self, verts, faces, node_xyz, nbr_idx, nbr_w, n_gaussians_per_surface_triangle=6,
                  skinning_method="hybrid", spatial_extent=3.8, vertex_colors=None, log_scales=None, complex_numbers=None,
                  densities=None, sh_dc=None, deformation_kwargs=None, deformation_lr=0.00032, grid_lr=0.0032,
-                 d_scale=False, init_gs_opacity=0.5, init_gs_scales_s=1.7, learn_opacities=True, device="cuda"):
+                 d_scale=False, init_gs_opacity=0.5, init_gs_scales_s=1.7, learn_opacities=True, sh_levels=1, device="cuda"):
         """Defaults of the optional static state follow ``SuGaRModel.Config`` (sugar.py:35-72: init_gs_opacity 0.5,
         init_gs_scales_s 1.7; 0.9999 when the opacities are not learnt, :100-107); a dynamic-stage run normally loads the
         static stage's checkpoint over them (``weights``)."""
@@ -118,7 +125,8 @@ class DynamicSuGaR(nn.Module):
             colors = (T(vertex_colors)[faces][:, None] * bary[None]).sum(-2).reshape(-1, 3)
             sh_dc = RGB2SH(colors).unsqueeze(1)
         self._sh_coordinates_dc = nn.Parameter(T(sh_dc).reshape(N, 1, 3), requires_grad=False)
-        self._sh_coordinates_rest = nn.Parameter(torch.zeros(N, 0, 3, device=dev), requires_grad=False)
+        self.sh_levels = _check_sh_levels(sh_levels)
+        self._sh_coordinates_rest = nn.Parameter(torch.zeros(N, self.sh_levels ** 2 - 1, 3, device=dev), requires_grad=False)   # sugar.py:231
         if densities is None:
             o0 = init_gs_opacity if learn_opacities else 0.9999              # sugar.py:100-107
             densities = torch.full((N, 1), math.log(o0 / (1.0 - o0)), device=dev)
@@ -150,7 +158,7 @@ class DynamicSuGaR(nn.Module):
         kw.update(deformation_kwargs or {})
         self._deformation = DeformationNetwork(**kw).to(dev)
         self.training_setup_dynamic(deformation_lr, grid_lr)
-        self.active_sh_degree = 0
+        self.active_sh_degree = self.sh_levels - 1
         self._static_cache = None
         self._deformed_vert_positions = {}
         self.global_step = 0
@@ -236,8 +244,14 @@ class DynamicSuGaR(nn.Module):
     def get_features(self):
         return torch.cat([self._sh_coordinates_dc, self._sh_coordinates_rest], dim=1)
 
-    def get_points_rgb(self):
-        return self._static()["rgb"]
+    def get_points_rgb(self, camera_centers=None):
+        """sugar.py:640-661: the DC colour for sh_levels == 1 (`camera_centers` ignored), else the clamped view-dependent colour of
+        the static points seen from ONE camera centre."""
+        if self.sh_levels == 1:
+            return self._static()["rgb"]
+        if camera_centers is None:
+            raise ValueError("camera_centers must be provided.")
+        return geo.points_rgb_sh(self.get_features, self.get_xyz, camera_centers, self.sh_levels)
 
     # ------------------------------------------------------------------ optimiser (dynamic_sugar.py:167-279, sugar.py:406-416)
     def training_setup_dynamic(self, deformation_lr=0.00032, grid_lr=0.0032):
@@ -360,7 +374,7 @@ class SuGaR(nn.Module):
     def __init__(self, verts, faces, n_gaussians_per_surface_triangle=6, spatial_extent=3.8, vertex_colors=None,
                  learn_positions=True, learn_opacities=True, learn_scales=True, freeze_gaussians=False,
                  position_lr=0.00048, feature_lr=0.001, opacity_lr=0.02, scaling_lr=0.005, rotation_lr=0.001,
-                 spatial_lr_scale=10.0, init_gs_opacity=0.9, init_gs_scales_s=1.3, color_clip=2.0, device="cuda"):
+                 spatial_lr_scale=10.0, init_gs_opacity=0.9, init_gs_scales_s=1.3, color_clip=2.0, sh_levels=1, device="cuda"):
         """The keyword defaults are the values configs/sugar_static_refine.yaml ships (learning rates :49-58, init_gs_opacity
         0.9, init_gs_scales_s 1.3 :64-66); ``SuGaRModel.Config``'s own defaults (sugar.py:35-72: 0.5, 1.7, lr 0.001 / 0.01 /
         0.05 / 0.005 / 0.005) are what threestudio_host.SuGaRModel passes when a cfg leaves them out."""
@@ -372,7 +386,8 @@ class SuGaR(nn.Module):
         F_, V = int(faces.shape[0]), int(verts.shape[0])
         N = F_ * G
         self.cfg_n_gaussians_per_surface_triangle = G
-        self.active_sh_degree = 0
+        self.sh_levels = _check_sh_levels(sh_levels)
+        self.active_sh_degree = self.sh_levels - 1
         self.register_buffer("_surface_mesh_faces", faces)
         self.register_buffer("_bary", geo.bary_coords(G, dev))
         self.surface_mesh_thickness = nn.Parameter(T(spatial_extent / 1_000_000), requires_grad=False)
@@ -381,7 +396,8 @@ class SuGaR(nn.Module):
             vertex_colors = torch.full((V, 3), 0.5, device=dev)
         colors = (T(vertex_colors)[faces][:, None] * self._bary[None]).sum(-2).reshape(-1, 3)    # sugar.py:209-224
         self._sh_coordinates_dc = nn.Parameter(RGB2SH(colors).unsqueeze(1), requires_grad=not freeze_gaussians)
-        self._sh_coordinates_rest = nn.Parameter(torch.zeros(N, 0, 3, device=dev), requires_grad=not freeze_gaussians)
+        self._sh_coordinates_rest = nn.Parameter(torch.zeros(N, self.sh_levels ** 2 - 1, 3, device=dev),
+                                                 requires_grad=not freeze_gaussians)                  # sugar.py:231
         o0 = init_gs_opacity if learn_opacities else 0.9999                                       # sugar.py:100-107
         self.all_densities = nn.Parameter(torch.full((N, 1), math.log(o0 / (1.0 - o0)), device=dev), requires_grad=learn_opacities)
         self._color_clip_cfg = color_clip
@@ -440,8 +456,14 @@ class SuGaR(nn.Module):
         """``sh_coordinates`` (sugar.py:457-462): the DC term clipped to +-color_clip."""
         return torch.cat([self._sh_coordinates_dc.clip(-self.color_clip, self.color_clip), self._sh_coordinates_rest], dim=1)
 
-    def get_points_rgb(self):
-        return geo.points_rgb(self._sh_coordinates_dc)
+    def get_points_rgb(self, camera_centers=None):
+        """sugar.py:640-661: SH2RGB of the DC term for sh_levels == 1 (`camera_centers` ignored), else the clamped view-dependent
+        colour of ``get_features`` seen from ONE camera centre (HIP, ``geometry.points_rgb_sh``)."""
+        if self.sh_levels == 1:
+            return geo.points_rgb(self._sh_coordinates_dc)
+        if camera_centers is None:
+            raise ValueError("camera_centers must be provided.")
+        return geo.points_rgb_sh(self.get_features, self.get_xyz, camera_centers, self.sh_levels)
 
     def get_rendered_rgb(self):
         """The colours the reference's static renderer blends: it hands ``shs = get_features`` to the rasterizer

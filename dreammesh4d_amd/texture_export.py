@@ -250,6 +250,9 @@ def canonical_gaussians(geometry):
     """(means3D, rotations, scales, opacities, colors6) of the canonical Gaussians as the reference renders them with no timestamp
     (C/renderer/diff_sugar_rasterizer_temporal.py:149-157: ``shs = get_features``; the rasterizer's degree-0 SH colour is
     max(SH2RGB(dc), 0)); the normal half of colors6 is zero (no normal pass in that branch)."""
+    from .geometry import require_sh_levels_1
+
+    require_sh_levels_1(geometry, "texture_export.canonical_gaussians")
     rgb = geometry.get_points_rgb().clamp_min(0.0)
     return (geometry.get_xyz, geometry.get_rotation, geometry.get_scaling, geometry.get_opacity.reshape(-1),
             torch.cat([rgb, torch.zeros_like(rgb)], 1))

@@ -39,6 +39,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import geometry as _geo
 from . import renderer as _renderer
 from . import shims as _shims
 from . import sugar as _sugar
@@ -379,7 +380,7 @@ class SuGaRModel(_sugar.SuGaR, Updateable):
                          learn_scales=c.learn_surface_mesh_scales, freeze_gaussians=c.freeze_gaussians,
                          position_lr=c.position_lr, feature_lr=c.feature_lr, opacity_lr=c.opacity_lr, scaling_lr=c.scaling_lr,
                          rotation_lr=c.rotation_lr, spatial_lr_scale=c.spatial_lr_scale, init_gs_opacity=c.init_gs_opacity,
-                         init_gs_scales_s=c.init_gs_scales_s, color_clip=c.color_clip, device=get_device())
+                         init_gs_scales_s=c.init_gs_scales_s, color_clip=c.color_clip, sh_levels=c.sh_levels, device=get_device())
         if c.weights is not None:
             from .wire_formats import load_module_weights
 
@@ -433,7 +434,8 @@ class DynamicSuGaRModel(_sugar.DynamicSuGaR, Updateable):
                          skinning_method=c.skinning_method, spatial_extent=c.spatial_extent,
                          vertex_colors=colors if c.gs_color_inherit_vertices else None, deformation_lr=c.deformation_lr,
                          grid_lr=c.grid_lr, d_scale=c.d_scale, init_gs_opacity=c.init_gs_opacity,
-                         init_gs_scales_s=c.init_gs_scales_s, learn_opacities=c.learn_surface_mesh_opacity, device=dev)
+                         init_gs_scales_s=c.init_gs_scales_s, learn_opacities=c.learn_surface_mesh_opacity, sh_levels=c.sh_levels,
+                         device=dev)
         self.num_frames, self.dynamic_mode = c.num_frames, c.dynamic_mode
         if c.static_learnable:
             # dynamic_sugar.py:79-87: the static SuGaR tensors keep requires_grad (they receive gradients -- the FULL blend
@@ -806,6 +808,7 @@ class SuGaR4DGen(_SystemBase):
         H, W = int(data.height), int(data.width)
         cam = data.ref_camera()
         self.view_renderer = views.ViewRenderer(g.graph, g.topo, H, W, cam.tanfov, method=g.skinning_method)
+        _geo.require_sh_levels_1(g, "the dynamic stage (DynamicStage / the step object)")
         static = {"q_static": g.static_quaternions, "scales": g.get_scaling, "opacities": g.get_opacity, "rgb": g.get_points_rgb()}
         loss = dict(cfg.get("loss", {}))
         faces = g.get_faces.detach().cpu().numpy()

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .geometry import reject_sh_coefficients
 from .ops import DEFAULT_GRAD_MODE, GRAD_MODES, METHODS, DeformGraph, MeshTopology
 
 vp = C.c_void_p
@@ -296,6 +297,7 @@ def render_views(renderer: ViewRenderer, dx, dr, ds, d_opacity, q_static, scales
 
     means2D [B,N,3] (optional, zeros with requires_grad): the reference's screen-space gradient carrier
     (``viewspace_points``); its gradient is dL/d(mean2D) of every view."""
+    reject_sh_coefficients(rgb, "render_views")
     m = renderer.method
     args = (renderer, dx, dr, ds if m != 1 else None, d_opacity if m == 2 else None, q_static, scales, opacities, rgb,
             viewmats, projmats, bg6, frame_index, means2D)

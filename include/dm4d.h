@@ -13,6 +13,7 @@
  *                         C/renderer/diff_sugar_rasterizer_temporal.py:129-178,202-211 and
  *                         C/renderer/diff_sugar_rasterizer_normal.py:117-132,161-170,186-195
  *   dm4d_mark_visible     GaussianRasterizer.markVisible (same package)
+ *   dm4d_sh_eval_*        SuGaR.get_points_rgb with sh_levels > 1, C/geometry/sugar.py:640-661 (eval_sh :733-820)
  *   dm4d_dist2_knn3       simple_knn._C.distCUDA2 (requirements.txt:50), call site
  *                         C/geometry/gaussian_base.py:435-438
  *   dm4d_skin_*           C/geometry/dynamic_sugar.py:408-465,487-613 (+ C/utils/dual_quaternions.py)
@@ -47,7 +48,7 @@ typedef void *dm4d_stream_t;   /* hipStream_t */
 /* ABI version = 100 * major + round.  A binding built against this header checks dm4d_version() == DM4D_ABI_VERSION when it loads the
  * library (dreammesh4d_amd/_lib.py does).  Entry points are never changed in place from round 5 on: a new argument is a new symbol
  * (dm4d_adamw_step beside dm4d_adamw_message, dm4d_normal_consistency_backward_scratch beside dm4d_normal_consistency_backward). */
-#define DM4D_ABI_VERSION 106
+#define DM4D_ABI_VERSION 107
 int dm4d_version(void);
 const char *dm4d_last_error(void);
 /* Number of HIP devices visible / name of device `dev` (host helpers for the loader). */
@@ -72,7 +73,9 @@ typedef struct dm4d_raster_settings {
     float tanfovx;
     float tanfovy;
     float scale_modifier;
-    int32_t sh_degree;          /* only 0 is implemented (the reference never uses more) */
+    int32_t sh_degree;          /* 0..3 with shs; sh_coeffs >= (sh_degree + 1)^2.  Degree > 0 is view-dependent and reads campos
+                                   (dm4d_sh_eval_forward is its colour stage).  The batched entry points (dm4d_views_*,
+                                   dm4d_gviews_*, dm4d_step_*) take one colour array for all views: no SH there */
     int32_t prefiltered;
     int32_t debug;
     const float *bg;            /* [dev] [3]  */
@@ -140,7 +143,10 @@ int dm4d_rasterize_overflowed(const void *geom, dm4d_stream_t stream);
 /* Backward of prepare+render.  dL_ddepth / dL_dalpha may be NULL (treated as zero).
  * Output gradient pointers may be NULL when not wanted, except dL_dmeans2D and
  * dL_dmeans3D.  `grad` is scratch of dm4d_raster_grad_bytes(record_capacity), record_capacity >= R.
- * Deterministic: no floating-point atomics anywhere. */
+ * Deterministic: no floating-point atomics anywhere.
+ * With shs and sh_degree > 0, dL_dcolors [N,3] and dL_dsh are both required: dL_dcolors receives dL/drgb (the gradient of
+ * the evaluated colour, before the clamp), from which dm4d_sh_eval_backward's kernel fills every coefficient of dL_dsh
+ * and adds the view-direction term to dL_dmeans3D. */
 int dm4d_rasterize_backward(const dm4d_raster_settings *s, const dm4d_raster_inputs *in,
                             const int32_t *radii, const void *geom, const void *binning, int64_t capacity,
                             const void *image, void *grad, int64_t record_capacity,
@@ -187,6 +193,20 @@ int dm4d_debug_sort_trace(void *trace);
 /* markVisible: present[i] = view-space z > 0.2 */
 int dm4d_mark_visible(int32_t N, const float *means3D, const float *viewmatrix, uint8_t *present,
                       dm4d_stream_t stream);
+
+/* View-dependent colour from spherical harmonics, SuGaR.get_points_rgb's sh_levels > 1 branch (C/geometry/sugar.py:640-661,
+ * eval_sh at :733-820): dir = normalize(means3D - campos), rgb = max(sum_{k < (degree+1)^2} B_k(dir) shs[:,k,:] + 0.5, 0),
+ * clamped = (that sum + 0.5 < 0).  degree 0..3, M >= (degree + 1)^2 stored coefficients of which the first (degree + 1)^2
+ * are read; a mean equal to campos has the zero direction.  One lane per Gaussian, no atomics. */
+int dm4d_sh_eval_forward(int32_t N, int32_t degree, int32_t M, const float *means3D /* [dev] [N,3] */,
+                         const float *campos /* [dev] [3] */, const float *shs /* [dev] [N,M,3] */,
+                         float *rgb /* [dev] [N,3] */, uint8_t *clamped /* [dev] [N,3] */, dm4d_stream_t stream);
+/* Its backward (autograd of C/geometry/sugar.py:640-661): dL_dsh[:,k,:] = clamped ? 0 : B_k(dir) dL_drgb for
+ * k < (degree + 1)^2 and exact zeros for the other coefficients; dL_dmeans3D is the chain through dir and its
+ * normalisation, exact zeros where the mean equals campos.  Both outputs are written, not accumulated. */
+int dm4d_sh_eval_backward(int32_t N, int32_t degree, int32_t M, const float *means3D, const float *campos,
+                          const float *shs, const uint8_t *clamped, const float *dL_drgb /* [dev] [N,3] */,
+                          float *dL_dsh /* [dev] [N,M,3] */, float *dL_dmeans3D /* [dev] [N,3] */, dm4d_stream_t stream);
 
 /* ------------------------------------------------------------------ Zero123 SDS step: GroupNorm (+ SiLU) over NHWC activations */
 
