@@ -124,14 +124,20 @@ __device__ __forceinline__ v3 so3_exp_grad(v3 r, q4 g)
 
 // ---- pypose's convention -------------------------------------------------------------------------------------------
 // g Jl(x) and g Jl^-1(x) (row vector times the left Jacobian of SO(3) / its inverse), K = hat(x):
-//   Jl = I + (1 - cos t)/t^2 K + (t - sin t)/t^3 K^2      Jl^-1 = I - K/2 + (1/t^2 - (1 + cos t)/(2 t sin t)) K^2
+//   Jl = I + (1 - cos t)/t^2 K + (t - sin t)/t^3 K^2      Jl^-1 = I - K/2 + (1/t^2 - cot(t/2)/(2 t)) K^2
 //   g K = g x x,  g K^2 = (g x x) x x
 __device__ __forceinline__ v3 row_times_Jl(v3 x, v3 g)
 {
     const float t2 = dot(x, x), t = sqrtf(t2);
     float c1, c2;
     if (t < 1e-3f) { c1 = 0.5f - t2 / 24.f; c2 = 1.f / 6.f - t2 / 120.f; }
-    else { c1 = (1.f - cosf(t)) / t2; c2 = (t - sinf(t)) / (t2 * t); }
+    else {
+        // 1 - cos t as 2 sin^2(t / 2): the difference loses log2(2 / t^2) bits (c1 off by 6 % at t = 1e-3, 0.06 % at 1e-2: 3e-5 /
+        // 3e-6 of the gradient).  t - sin t cancels too, but its absolute error eps * t enters the result as eps * |g|: harmless.
+        const float sh = sinf(0.5f * t);
+        c1 = 2.f * sh * sh / t2;
+        c2 = (t - sinf(t)) / (t2 * t);
+    }
     const v3 gk = cross(g, x), gkk = cross(gk, x);
     return g + c1 * gk + c2 * gkk;
 }
@@ -140,7 +146,7 @@ __device__ __forceinline__ v3 row_times_Jl_inv(v3 x, v3 g)
     const float t2 = dot(x, x), t = sqrtf(t2);
     float c2;
     if (t < 1e-3f) c2 = 1.f / 12.f + t2 / 720.f;
-    else c2 = (1.f - 0.5f * t * (1.f + cosf(t)) / sinf(t)) / t2;
+    else c2 = (1.f - 0.5f * t * cosf(0.5f * t) / sinf(0.5f * t)) / t2;      // cot(t / 2) of the half angle: (1 + cos t) / sin t is 0 / 0 at t = pi (w ~ 0), where Jl^-1 is smooth
     const v3 gk = cross(g, x), gkk = cross(gk, x);
     return g - 0.5f * gk + c2 * gkk;
 }

@@ -62,10 +62,17 @@ def bary_table(n=6, dtype=torch.float32):
 
 
 # ----------------------------------------------------------------------------- quaternion algebra (x,y,z,w)
+def _series_below(x):
+    """Series / generic switch of Log and Exp: pypose's (float32 eps) in float64.  A float32 evaluation of this file (the
+    float32 error floor the kernels are measured against, tests/skinning_edge_cases.py) switches at 1e-3, where the
+    truncated series are still exact to 1e-12."""
+    return 1e-3 if x.dtype == torch.float32 else EPS32
+
+
 def so3_log(q):
     v, w = q[..., :3], q[..., 3:]
     vn = v.norm(dim=-1, keepdim=True)
-    small = vn < EPS32
+    small = vn < _series_below(vn)
     vn_safe = torch.where(small, torch.ones_like(vn), vn)
     generic = 2.0 * torch.atan(vn_safe / w) / vn_safe
     series = 2.0 / w - (2.0 / 3.0) * vn * vn / (w * w * w)
@@ -74,7 +81,7 @@ def so3_log(q):
 
 def so3_exp(x):
     t = x.norm(dim=-1, keepdim=True)
-    small = t < EPS32
+    small = t < _series_below(t)
     t_safe = torch.where(small, torch.ones_like(t), t)
     imag = torch.where(small, 0.5 - t * t / 48.0 + t ** 4 / 3840.0, torch.sin(0.5 * t_safe) / t_safe)
     real = torch.where(small, 1.0 - t * t / 8.0 + t ** 4 / 384.0, torch.cos(0.5 * t))
@@ -112,23 +119,41 @@ def _hat_row(g, x):
     return torch.linalg.cross(g, x, dim=-1)
 
 
-def _row_times_Jl(x, g):
-    t2 = (x * x).sum(-1, keepdim=True)
+def _jl_coeffs(t2):
+    """c1 = (1 - cos t) / t^2 and c2 = (t - sin t) / t^3 of the left Jacobian Jl = I + c1 K + c2 K^2, from t^2.
+    c1 in the cancellation-free form 2 sin^2(t / 2) / t^2 (the textbook form loses |log2 t^2| bits); c2 by its series
+    below t = 0.1 (next term t^8 / 39916800: < 2e-15 relative there), where t - sin t has cancelled 3 digits at most above.
+    Pinned to 1e-12 relative against 50-digit arithmetic (tests/test_skinning_edges_cpu.py)."""
     t = t2.sqrt()
-    small = t < 1e-6
-    ts = torch.where(small, torch.ones_like(t), t)
-    c1 = torch.where(small, 0.5 - t2 / 24.0, (1.0 - torch.cos(ts)) / (ts * ts))
-    c2 = torch.where(small, 1.0 / 6.0 - t2 / 120.0, (ts - torch.sin(ts)) / (ts ** 3))
+    tiny = t2 == 0
+    ts = torch.where(tiny, torch.ones_like(t), t)
+    sh = torch.sin(0.5 * ts) / (0.5 * ts)
+    c1 = torch.where(tiny, torch.full_like(t, 0.5), 0.5 * sh * sh)
+    small = t < 0.1
+    tg = torch.where(small, torch.ones_like(t), t)
+    c2 = torch.where(small, 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0 - t2 * t2 * t2 / 362880.0, (tg - torch.sin(tg)) / (tg ** 3))
+    return c1, c2
+
+
+def _jl_inv_coeff(t2):
+    """c2 = (1 - (t / 2) cot(t / 2)) / t^2 of Jl^-1 = I - K / 2 + c2 K^2, from t^2.  cot(t / 2) as cos / sin of the half
+    angle: (1 + cos t) / sin t is 0 / 0 at t = pi, where the function itself is smooth.  Series below t = 0.3 (next term
+    691 t^10 / 1307674368000: < 5e-14 relative there); above, 1 - (t / 2) cot(t / 2) > 7e-3 has lost 2 digits at most."""
+    t = t2.sqrt()
+    small = t < 0.3
+    tg = torch.where(small, torch.ones_like(t), t)
+    series = 1.0 / 12.0 + t2 / 720.0 + t2 ** 2 / 30240.0 + t2 ** 3 / 1209600.0 + t2 ** 4 / 47900160.0
+    return torch.where(small, series, (1.0 - 0.5 * tg * torch.cos(0.5 * tg) / torch.sin(0.5 * tg)) / (tg * tg))
+
+
+def _row_times_Jl(x, g):
+    c1, c2 = _jl_coeffs((x * x).sum(-1, keepdim=True))
     gk = _hat_row(g, x)
     return g + c1 * gk + c2 * _hat_row(gk, x)
 
 
 def _row_times_Jl_inv(x, g):
-    t2 = (x * x).sum(-1, keepdim=True)
-    t = t2.sqrt()
-    small = t < 1e-6
-    ts = torch.where(small, torch.ones_like(t), t)
-    c2 = torch.where(small, 1.0 / 12.0 + t2 / 720.0, (1.0 - 0.5 * ts * (1.0 + torch.cos(ts)) / torch.sin(ts)) / (ts * ts))
+    c2 = _jl_inv_coeff((x * x).sum(-1, keepdim=True))
     gk = _hat_row(g, x)
     return g - 0.5 * gk + c2 * _hat_row(gk, x)
 

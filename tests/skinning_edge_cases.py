@@ -1,0 +1,249 @@
+"""Inputs, references and the error measure of tests/test_skinning_edges_{cpu,gpu}.py (TEST INFRASTRUCTURE).
+
+The skinning kernels (dreammesh4d_amd/csrc/skinning.hip) switch between a series and a generic formula at hard-coded
+magnitudes (1.19e-7 in so3_log / so3_exp, 1e-4 in so3_log_grad, 1e-3 in so3_exp_grad / row_times_Jl / row_times_Jl_inv),
+evaluate atanf(u / w) for either sign of w, and clamp the hybrid blend at eta + 0.4 = 1.  The scenes here put node rotations
+(and, for the face kernels, vertex rotations) into one MAGNITUDE CLASS per node around each of those points, wire the graph
+so that half the vertices have all K neighbours in ONE class (the blended rotation vector sum_k w_k Log q_k then lies in the
+band as well: so3_exp_grad / row_times_Jl see the blend, not the node) and the other half mix classes, leave some nodes
+unreferenced, zero some weights, and optionally make one node a neighbour of every vertex.
+
+Error measure, per element of a gradient row r (a node, or a vertex of the face kernels):
+    ratio = |x - ref| / (|ref| + s_r),   s_r = sum over the records added into row r of the norm of that record's upstream
+gradient (so: the row's mean upstream-gradient norm times its number of records).  An unreferenced row has s_r = 0 and ref = 0:
+anything but an exact 0 there is an infinite ratio.  F32_FLOOR is the worst ratio of a float32 CPU evaluation of the oracle's
+own formulas against its float64 evaluation; the kernels get 8 x that (other summation order; __expf, atanf, sinf, cosf at a
+few ulp each).
+"""
+import numpy as np
+import torch
+
+from oracle import skinning as sk
+
+D = torch.float64
+
+# name -> (lo, hi) of |dr_xyz| (log-uniform), or a callable below
+BANDS = {"eps": (1e-9, 1e-6),        # around kEps = 1.19e-7 after normalisation (so3_log / so3_exp)
+         "1e-4": (3e-5, 3e-4),       # around so3_log_grad's switch
+         "1e-3": (3e-4, 3e-2),       # around and above the 1e-3 switches (|Log q| ~ 2 |dr_xyz|)
+         "above_1e-3": (5e-4, 1.5e-3)}   # |Log q| in [1e-3, 3e-3]: right above the switch, where a generic formula cancels most
+CLASSES = ["zero", "eps", "1e-4", "1e-3", "above_1e-3", "0.15", "1", "3", "w0"]
+N_UNREF = 6                          # the last nodes of every graph are referenced by no vertex
+DQS_MIN_BLEND = 0.25                 # |sum_k w_k q_k| below this: the reference's own singularity (antipodal neighbours), left out
+CLAMP_EXCLUDE = 1e-6                 # |eta + 0.4 - 1| below this: the clamp's side is undecidable in float32
+
+
+def class_rows(name, n, rng):
+    """n rows of the rotation head's raw output `dr` (x, y, z, w; the node rotation is normalize(dr + (0, 0, 0, 1)))."""
+    d = rng.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    if name == "zero":
+        return np.zeros((n, 4), np.float32)
+    if name in BANDS:
+        lo, hi = BANDS[name]
+        mag = np.exp(rng.uniform(np.log(lo), np.log(hi), size=(n, 1)))
+        return np.concatenate([mag * d, 0.5 * mag * rng.normal(size=(n, 1))], 1).astype(np.float32)
+    if name == "0.15":
+        return (0.15 * rng.normal(size=(n, 4))).astype(np.float32)
+    if name in ("1", "3"):           # angles up to pi; dr.w < -1 (w < 0) in a sixth / a third of the rows
+        return (float(name) * rng.normal(size=(n, 4))).astype(np.float32)
+    if name == "w0":                 # w = dr.w + 1 in +-[1e-5, 1e-3]: atanf(u / w) near +-pi/2, |Log q| near pi
+        w = np.exp(rng.uniform(np.log(1e-5), np.log(1e-3), size=(n, 1))) * np.where(np.arange(n)[:, None] % 2 == 0, 1.0, -1.0)
+        return np.concatenate([0.3 * rng.uniform(0.7, 1.3, size=(n, 1)) * d, -1.0 + w], 1).astype(np.float32)
+    raise ValueError(name)
+
+
+def skin_scene(classes, K, V, M=150, seed=0, hub=False):
+    rng = np.random.default_rng(seed)
+    n_ref = M - N_UNREF
+    node_class = np.array([i % len(classes) for i in range(M)])
+    dr = np.zeros((M, 4), np.float32)
+    for c, name in enumerate(classes):
+        rows = np.nonzero(node_class == c)[0]
+        dr[rows] = class_rows(name, len(rows), rng)
+    p = rng.normal(size=(V, 3))
+    verts = (0.6 * p / np.linalg.norm(p, axis=1, keepdims=True) * rng.uniform(0.5, 1.0, size=(V, 1))).astype(np.float32)
+    idx = np.zeros((V, K), np.int64)
+    near = (np.arange(M) // len(classes)) % 2 == 0      # nodes whose opacity puts the hybrid blend next to its clamp (below)
+    for v in range(V):
+        pool = np.arange(n_ref)
+        if v % 2 == 0:               # all K neighbours of one class
+            pool = pool[node_class[:n_ref] == (v // 2) % len(classes)]
+            if v % 4 == 0:           # ... and all of them next to the clamp
+                pool = pool[near[pool]]
+        idx[v] = rng.choice(pool, size=K, replace=len(pool) < K)
+    if hub:
+        idx[:, 0] = 0                # node 0: a neighbour of every vertex (V records: the lane-stride loop of the node kernel)
+    w = rng.random((V, K)) + 0.05
+    if K >= 2:
+        z = np.arange(V) % 5 == 0
+        w[z, rng.integers(0, K, size=V)[z]] = 0.0          # weights that are exactly 0
+    w = (w / w.sum(1, keepdims=True)).astype(np.float32)
+    # opacity head: sigmoid(0.405) = 0.6 puts eta + 0.4 at the clamp.  Half the nodes scatter widely (both sides), half sit
+    # within 2e-3 of it (`near`: vertices whose neighbours are all of these land within 1e-3 of the clamp, on either side)
+    do = np.where(near, 0.405 + rng.uniform(-2e-3, 2e-3, size=M), 0.405 + rng.normal(size=M)).astype(np.float32)
+    return {"verts": verts, "nbr_idx": idx, "nbr_w": w, "M": M, "K": K, "V": V, "node_class": node_class, "classes": list(classes),
+            "dx": (0.05 * rng.normal(size=(M, 3))).astype(np.float32), "dr": dr,
+            "ds": (0.05 * rng.normal(size=(M, 6))).astype(np.float32), "do": do}
+
+
+def skin_upstream(sc, method, seed=1, clamp_margin=CLAMP_EXCLUDE):
+    """Upstream gradients (g_xyz [V,3], g_rot [V,4]) and the mask of vertices whose position takes part in the comparison.
+    g_xyz is zero on the vertices left out (their node gradients would otherwise carry the excluded quantity)."""
+    t = lambda a: torch.tensor(a, dtype=D)
+    idx, w = torch.tensor(sc["nbr_idx"]), t(sc["nbr_w"])
+    _, q, _, op = sk.node_attributes(t(sc["dx"]), t(sc["dr"]), None, t(sc["do"])[:, None])
+    keep = torch.ones(sc["V"], dtype=torch.bool)
+    if method in ("dqs", "hybrid"):
+        keep &= (q[idx] * w[..., None]).sum(1).norm(dim=-1) >= DQS_MIN_BLEND
+    if method == "hybrid":
+        eta = (w[..., None] * op[idx]).sum(1)[:, 0] + 0.4
+        keep &= (eta - 1.0).abs() >= clamp_margin
+        sc["eta"] = eta.numpy()
+    g = torch.Generator().manual_seed(seed)
+    gx = torch.randn(sc["V"], 3, generator=g) * keep[:, None]
+    gr = torch.randn(sc["V"], 4, generator=g)
+    return gx, gr, keep.numpy()
+
+
+def skin_reference(sc, method, grad_mode, gx, gr, dtype=D):
+    """oracle/skinning.py on the CPU in `dtype` on the float32 inputs: (xyz, rot, {leaf: gradient})."""
+    t = lambda a: torch.tensor(a).to(dtype)
+    leaves = {k: t(sc[k]).requires_grad_(True) for k in ("dx", "dr", "ds", "do")}
+    trans, q, S, op = sk.node_attributes(leaves["dx"], leaves["dr"], leaves["ds"], leaves["do"][:, None])
+    xyz, rot = sk.skin_vertices(t(sc["verts"]), torch.tensor(sc["nbr_idx"]), t(sc["nbr_w"]), trans, q, S, op, method, grad_mode=grad_mode)
+    torch.autograd.backward([xyz, rot], [gx.to(dtype), gr.to(dtype)])
+    grads = {k: (torch.zeros_like(v) if v.grad is None else v.grad).numpy().astype(np.float64).reshape(sc["M"], -1) for k, v in leaves.items()}
+    return xyz.detach().numpy(), rot.detach().numpy(), grads
+
+
+def skin_row_scale(sc, gx, gr):
+    """s_m = sum over the (vertex, k) records of node m of |(g_xyz, g_rot)[vertex]|."""
+    n = torch.cat([gx, gr], 1).to(D).norm(dim=1).numpy()
+    s = np.zeros(sc["M"])
+    np.add.at(s, sc["nbr_idx"].reshape(-1), np.repeat(n, sc["K"]))
+    return s
+
+
+def worst_ratio(x, ref, s):
+    x, ref = np.asarray(x, np.float64).reshape(len(s), -1), np.asarray(ref, np.float64).reshape(len(s), -1)
+    err, den = np.abs(x - ref), np.abs(ref) + np.asarray(s)[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(err == 0, 0.0, err / den)
+    return float(np.nan_to_num(r, nan=np.inf).max()) if r.size else 0.0
+
+
+def skin_ratios(sc, method, got, ref, s):
+    """Worst ratio per gradient the method has (lbs: no opacity; dqs: neither strain nor opacity)."""
+    names = ["dx", "dr"] + (["ds"] if method != "dqs" else []) + (["do"] if method == "hybrid" else [])
+    return {k: worst_ratio(got[k], ref[k], s) for k in names}
+
+
+# ------------------------------------------------------------------------------------------------ face -> Gaussians
+def face_scene(classes, G, n_faces=600, seed=0):
+    """A UV sphere whose vertex rotations come from `classes` in contiguous index blocks (a sphere's vertices are ordered ring by
+    ring, so most faces have three corners of one class and the faces between two blocks mix them), plus three zero-area
+    faces on nine vertices of their own."""
+    from dreammesh4d_amd import synthetic as syn
+
+    rng = np.random.default_rng(seed)
+    verts, faces = syn.uv_sphere(n_faces, 0.6)
+    V0 = len(verts)
+    a, b = verts[3], verts[40]
+    extra = np.stack([a, a, b, a, b, a, a, a, a]).astype(np.float32)                    # (a, a, b), (a, b, a), (a, a, a): an edge that is exactly 0
+    verts = np.concatenate([verts, extra]).astype(np.float32)
+    faces = np.concatenate([faces, V0 + np.arange(9).reshape(3, 3)]).astype(np.int64)
+    V, F = len(verts), len(faces)
+    vxyz = verts.copy()
+    vxyz[:V0] += (0.003 * rng.normal(size=(V0, 3))).astype(np.float32)     # well inside the shortest edge: no slivers (not the subject here)
+    vclass = (np.arange(V) * len(classes) // V) if len(classes) > 1 else np.zeros(V, int)
+    dr = np.zeros((V, 4), np.float32)
+    for c, name in enumerate(classes):
+        rows = np.nonzero(vclass == c)[0]
+        dr[rows] = class_rows(name, len(rows), rng)
+    q = torch.tensor(dr, dtype=D)
+    q[:, 3] += 1.0
+    vrot = torch.nn.functional.normalize(q, dim=-1).float().numpy()                     # "zero" rows: exactly (0, 0, 0, 1)
+    cplx = torch.tensor(rng.normal(size=(F * G, 2)))
+    qs = sk.static_quaternions(torch.tensor(vxyz[:V0], dtype=D), torch.tensor(faces[:-3]), cplx[:-3 * G], n_per_face=G)
+    ang = rng.uniform(0, 2 * np.pi, size=3 * G)                                         # the zero-area faces have no frame: any unit quaternion
+    qs_deg = torch.tensor(np.stack([np.cos(ang), np.sin(ang), 0 * ang, 0 * ang], 1))
+    return {"vxyz": vxyz, "vrot": vrot, "faces": faces, "F": F, "V": V, "V0": V0, "G": G, "qs": torch.cat([qs, qs_deg]).float().numpy(),
+            "classes": list(classes)}
+
+
+def face_upstream(sc, seed=2):
+    g = torch.Generator().manual_seed(seed)
+    N = sc["F"] * sc["G"]
+    return torch.randn(N, 3, generator=g), torch.randn(N, 4, generator=g), torch.randn(N, 3, generator=g)
+
+
+def face_reference(sc, grad_mode, gm, gq, gn, dtype=D):
+    """(means, rots, normals, dL/dvxyz, dL/dvrot).  The zero-area faces' normal gradient is dropped from the reference (the
+    1e-12 clamp makes it 1e12-scale); it reaches their own nine vertices only, which the comparison leaves out."""
+    t = lambda a: torch.tensor(a).to(dtype)
+    x, r = t(sc["vxyz"]).requires_grad_(True), t(sc["vrot"]).requires_grad_(True)
+    m, q, n = sk.face_gaussians(x, r, torch.tensor(sc["faces"]), t(sc["qs"]), n_per_face=sc["G"], grad_mode=grad_mode)
+    if gn is not None:
+        gn = gn.clone()
+        gn[-3 * sc["G"]:] = 0
+    ups = [(m, gm), (q, gq), (n, gn)]
+    torch.autograd.backward([a for a, g in ups if g is not None], [g.to(dtype) for a, g in ups if g is not None])
+    z = lambda v: (torch.zeros_like(v) if v.grad is None else v.grad).numpy().astype(np.float64)
+    return m.detach().numpy(), q.detach().numpy(), n.detach().numpy(), z(x), z(r)
+
+
+def face_row_scales(sc, gm, gq, gn):
+    """Per vertex: sum over its incident corners of the upstream norms that reach it.  A face normal's gradient reaches a
+    corner through |opposite edge| / |e1 x e2| (the norm of d normal / d corner), taken from the float64 geometry."""
+    G, F, V = sc["G"], sc["F"], sc["V"]
+    z = torch.zeros(F * G, dtype=D)
+    nm = gm.to(D).norm(dim=1) if gm is not None else z
+    nq = gq.to(D).norm(dim=1) if gq is not None else z
+    sum_m, sum_q = nm.view(F, G).sum(1).numpy(), nq.view(F, G).sum(1).numpy()
+    fv = sc["vxyz"].astype(np.float64)[sc["faces"]]
+    c = np.linalg.norm(np.cross(fv[:, 1] - fv[:, 0], fv[:, 2] - fv[:, 0]), axis=1)
+    gns = gn.to(D).view(F, G, 3).sum(1).norm(dim=1).numpy() if gn is not None else np.zeros(F)
+    sx, sr = np.zeros(V), np.zeros(V)
+    for j in range(3):
+        opp = np.linalg.norm(fv[:, (j + 1) % 3] - fv[:, (j + 2) % 3], axis=1)
+        np.add.at(sx, sc["faces"][:, j], sum_m + gns * opp / np.maximum(c, 1e-12))
+        np.add.at(sr, sc["faces"][:, j], sum_q)
+    return sx, sr
+
+
+# ------------------------------------------------------------------------------------------------ the cases
+def skin_cases(which):
+    """(label, scene) pairs.  "all": every class in one call, for each K; K = 4 (the DPP-quad kernel) also at sizes that leave
+    its last 64-quad block partial or almost empty, and with a hub node; "class": each class alone, at K = 1 (one or two
+    records per node, so one wrong record is not averaged away) and K = 4."""
+    if which == "all":
+        for K in (1, 2, 3, 4, 5, 8):
+            yield f"all/K{K}", skin_scene(CLASSES, K, 1500, seed=K)
+        for V in (1, 63, 64, 65, 1001):
+            yield f"all/K4/V{V}", skin_scene(CLASSES, 4, V, seed=100 + V)
+        for K in (4, 5):
+            yield f"hub/K{K}", skin_scene(CLASSES, K, 1500, seed=20 + K, hub=True)
+    else:
+        for K in (1, 4):
+            yield f"{which}/K{K}", skin_scene([which], K, 300, seed=10 + K)
+
+
+def face_cases(which):
+    if which == "all":
+        for G in (1, 3, 4, 6):
+            yield f"all/G{G}", face_scene(CLASSES, G, seed=G)
+    else:
+        for G in (1, 6):
+            yield f"{which}/G{G}", face_scene([which], G, seed=30 + G)
+
+
+METHODS = ("lbs", "dqs", "hybrid")
+MODES = ("exact", "pypose")
+
+# Worst ratio of the float32 evaluation of oracle/skinning.py against its float64 evaluation over every case above (all
+# classes, three methods, both gradient conventions, the face transform), measured on the CPU: 5.37e-7 (the w ~ 0 class alone
+# at K = 1, pypose convention, dL/d(dr); every other class stays below 2.4e-7, all classes in one call reach 4.8e-7).  test_skinning_edges_cpu.py::test_float32_floor_of_the_oracle_formulas re-measures it
+# and asserts that it does not exceed this figure.
+F32_FLOOR = 5.4e-7
+KERNEL_BOUND = 8 * F32_FLOOR         # rtol = atol of |hip - ref| <= rtol |ref| + atol s
