@@ -218,6 +218,7 @@ _SIGNATURES = {
                                            C.POINTER(MlpWeightsGrad), vp, vp]),
     "dm4d_arap_energy_forward": (C.c_int, [C.c_int32, C.c_int32] + [vp] * 9),
     "dm4d_arap_energy_backward": (C.c_int, [C.c_int32, C.c_int32] + [vp] * 11),
+    "dm4d_arap_fit_rotations": (C.c_int, [C.c_int32, C.c_int32] + [vp] * 8),
     "dm4d_grad_pack": (C.c_int, [C.POINTER(GradSegments), vp, vp]),
     "dm4d_grad_unpack": (C.c_int, [C.POINTER(GradSegments), vp, C.c_float, vp]),
     "dm4d_adamw_message": (C.c_int, [C.POINTER(GradSegments), C.POINTER(AdamwArgs), C.c_float, vp]),

@@ -13,6 +13,7 @@
 // of the edges that point at it -- no atomics, deterministic.
 #include <mutex>
 #include "common.h"
+#include "arap_fit.h"
 #include "../../include/dm4d.h"
 
 namespace dm4d {
@@ -35,8 +36,8 @@ __device__ __forceinline__ void edge_residual(const float *__restrict__ xi, cons
 // sphere have ~360 edges against a mean of 6: 33 / 75 us forward / backward, and 343 us for the normal-consistency gather
 // below, whose poles touch ~700 pair roles).  The order of the sum is fixed by the lane assignment: deterministic.
 constexpr int kSub = 8;
-template <int N>
-__device__ __forceinline__ void group_sum(float (&v)[N])
+template <typename F, int N>
+__device__ __forceinline__ void group_sum(F (&v)[N])
 {
 #pragma unroll
     for (int m = 1; m < kSub; m <<= 1)
@@ -116,6 +117,77 @@ __global__ __launch_bounds__(256) void k_arap_bwd(ArapAdj a, const float *__rest
 #pragma unroll
         for (int k = 0; k < 9; ++k) o[k] = ge * g[3 + k];
     }
+}
+
+
+// ---------------------------------------------------------------------------------------- ARAP: fitted rotations
+// compute_arap_energy(xyz_prime, vert_rotations=None) (arap_utils.py:195-214): the rotation of vertex i is fitted to its one-ring,
+//     S_i = sum_j w_ij e_ij e'_ij^T  (= P^T D P' of :197-198),   R_i = argmax over SO(3) of tr(R S_i)   (arap_fit.h)
+// and a vertex the reference calls unchanged (:201-202) gets S = 0, hence R = I.  Its rule is mirrored as written: `(P == P_prime)
+// .all(dim=1)` runs over the NEIGHBOURS, and torch.where(...)[0] then keeps a vertex if the edge components agree on AT LEAST ONE
+// coordinate axis (a deformation that moves only y and z leaves every vertex "unchanged").  The comparison is the reference's
+// float `==` on the float32 edge x'_i - x'_j against the stored rest edge; the covariance is summed in double from the float32
+// inputs (their differences and products are then exact, only the sum rounds), so R is the double fit rounded once to float32.
+//
+// A block owns kFitVerts consecutive vertices of one timestamp.  Gather: groups of kSub lanes walk one vertex each (as k_arap_fwd,
+// the poles of a uv sphere have ~360 edges), 256 / kSub vertices per pass, and park S in LDS; solve: one lane per vertex, so the
+// Jacobi sweeps run on full waves instead of on one lane in kSub.  No atomics, the order of every sum is fixed by the lane
+// assignment: deterministic.  flags (nullable) [T][V]: bit 0 = unchanged, bit 1 = det(S) < 0 (the reference's determinant flip).
+constexpr int kFitVerts = 256;
+__global__ __launch_bounds__(256) void k_arap_fit(ArapAdj a, const float *__restrict__ xyz, float *__restrict__ rot /* [T][V][9] */,
+                                                  uint8_t *__restrict__ flags)
+{
+    __shared__ double sS[9][kFitVerts];        // component-major: the solve's reads are conflict-free
+    __shared__ uint8_t sUnchanged[kFitVerts];
+    const int grp = threadIdx.x / kSub, sub = threadIdx.x % kSub, v0 = blockIdx.x * kFitVerts;
+    const size_t t = blockIdx.y;
+    xyz += t * a.V * 3;
+    for (int slot = grp; slot < kFitVerts; slot += 256 / kSub) {
+        const int i = v0 + slot;
+        if (i >= a.V) break;                   // (whole groups leave together)
+        float xi[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xi[k] = xyz[3 * (size_t)i + k];
+        double S[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        int same = 7;                          // bit c: every edge seen so far has e'[c] == e[c]
+        const int e1 = a.off[i + 1];
+#pragma unroll 2
+        for (int eidx = a.off[i] + sub; eidx < e1; eidx += kSub) {
+            const float *xj = xyz + 3 * (size_t)a.nbr[eidx], *e = a.e + 3 * (size_t)eidx;
+            const double w = a.w[eidx];
+            double ep[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (!(xi[c] - xj[c] == e[c])) same &= ~(1 << c);
+                ep[c] = (double)xi[c] - (double)xj[c];
+            }
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const double we = w * (double)e[r];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) S[3 * r + c] += we * ep[c];
+            }
+        }
+        group_sum(S);
+#pragma unroll
+        for (int m = 1; m < kSub; m <<= 1) same &= __shfl_xor(same, m, kSub);
+        if (sub == 0) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) sS[k][slot] = same ? 0.0 : S[k];
+            sUnchanged[slot] = same ? 1 : 0;
+        }
+    }
+    __syncthreads();
+    const int i = v0 + threadIdx.x;
+    if (i >= a.V) return;
+    double S[9], R[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) S[k] = sS[k][threadIdx.x];
+    fit_rotation(S, R);
+    float *o = rot + (t * a.V + i) * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o[k] = (float)R[k];
+    if (flags) flags[t * a.V + i] = (uint8_t)(sUnchanged[threadIdx.x] | (det3(S) < 0.0 ? 2 : 0));
 }
 
 
@@ -354,6 +426,22 @@ int dm4d_arap_energy_backward(int32_t T, int32_t V, const int32_t *csr_offsets, 
     ArapAdj a{V, csr_offsets, neighbors, reverse_edge, weights, rest_edges};
     hipLaunchKernelGGL(k_arap_bwd, dim3((unsigned)(((size_t)V * kSub + 255) / 256), T), dim3(256), 0, (hipStream_t)stream, a, xyz_prime, rotations, g_energy,
                        g_xyz, g_rotations);
+    DM4D_HIP_CHECK(hipGetLastError());
+    return DM4D_OK;
+}
+
+int dm4d_arap_fit_rotations(int32_t T, int32_t V, const int32_t *csr_offsets, const int32_t *neighbors, const float *weights,
+                            const float *rest_edges, const float *xyz_prime, float *rotations_out, uint8_t *flags_out,
+                            dm4d_stream_t stream)
+{
+    // (the fit reads no reverse-edge index: the checks are arap_check's with the output in the place of the rotations)
+    int rc = arap_check(T, V, csr_offsets, neighbors, csr_offsets, weights, rest_edges, xyz_prime, xyz_prime);
+    if (rc) return rc;
+    if (T == 0 || V == 0) return DM4D_OK;
+    if (!rotations_out) { set_error("arap: null output"); return DM4D_ERR_INVALID; }
+    ArapAdj a{V, csr_offsets, neighbors, nullptr, weights, rest_edges};
+    hipLaunchKernelGGL(k_arap_fit, dim3((unsigned)(((size_t)V + kFitVerts - 1) / kFitVerts), T), dim3(256), 0, (hipStream_t)stream, a, xyz_prime,
+                       rotations_out, flags_out);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
 }

@@ -1,13 +1,20 @@
 """Mesh regularisers of the dynamic stage: host mirror of ``ARAPCoach``
-(custom/threestudio-dreammesh4d/utils/arap_utils.py:17-224) for the way the system uses it --
-``compute_arap_energy(xyz_prime, vert_rotations)`` with the skinned vertex rotations, once per key frame and per
-inter-frame timestamp (system/sugar_4dgen.py:304-311,331-385) -- on one HIP launch for all timestamps
-(csrc/meshreg.hip, C ABI ``dm4d_arap_energy_*``).
+(custom/threestudio-dreammesh4d/utils/arap_utils.py:17-224) and its one public method
+``compute_arap_energy(xyz_prime, vert_rotations=None)``, on one HIP launch per step for all timestamps (csrc/meshreg.hip,
+C ABI ``dm4d_arap_energy_*`` / ``dm4d_arap_fit_rotations``):
+
+* rotations GIVEN -- the way the system calls it, with the skinned vertex rotations, once per key frame and per inter-frame
+  timestamp (system/sugar_4dgen.py:304-311,331-385): ``k_arap_fwd`` / ``k_arap_bwd``, gradients to both arguments;
+* rotations ``None`` -- the reference's default (:195-214): every vertex gets the rotation that best fits its one-ring
+  (covariance, SVD, ``R = W U^T``, determinant flip), here ``k_arap_fit`` (the maximiser of ``tr(R S)`` over SO(3) directly, no
+  SVD; csrc/arap_fit.h), then the same energy kernels.  The fitted ``R`` is a stationary point of the energy, so the gradient to
+  ``xyz_prime`` is ``k_arap_bwd`` with ``R`` held fixed: equal to the reference's autograd through ``torch.svd`` where that is
+  finite (tests/test_arap_fit_cpu.py), and finite where it is not.  ``fit_rotations`` returns the rotations themselves.
 
 The static part (one-ring neighbours, the reference's cotangent weights, rest edges) is computed once on the
 host with the reference's arithmetic, quirk included (dense branch of ``produce_cot_weights_nfmt``: the weight of
-the directed edge (f_a, f_b) of a face is assigned 0.5 * cot(angle at f_a) / 4, then W + W^T).  The SVD branch
-(rotations fitted from the deformation) is not on the dynamic stage's path and is not mirrored.
+the directed edge (f_a, f_b) of a face is assigned 0.5 * cot(angle at f_a) / 4, then W + W^T).  The kNN constructor branch
+(``faces=None``, open3d's KD-tree) is not mirrored.
 """
 import ctypes as C
 
@@ -76,8 +83,25 @@ class _ArapEnergy(torch.autograd.Function):
         return None, gx, gr
 
 
+def _fit_rotations(coach, x, want_flags=False):
+    """x [T,V,3] float32 contiguous on the coach's device -> R [T,V,3,3] (and the flag bytes [T,V])."""
+    L = _lib.lib()
+    dev = coach.device
+    T, V = int(x.shape[0]), coach.n_verts
+    R = torch.empty(T, V, 3, 3, dtype=torch.float32, device=dev)
+    flags = torch.empty(T, V, dtype=torch.uint8, device=dev) if want_flags else None
+    with torch.cuda.device(dev):
+        _lib.check(L.dm4d_arap_fit_rotations(T, V, coach._off.data_ptr(), coach._nbr.data_ptr(), coach._w.data_ptr(),
+                                             coach._e.data_ptr(), x.data_ptr(), R.data_ptr(),
+                                             None if flags is None else flags.data_ptr(),
+                                             torch.cuda.current_stream(dev).cuda_stream), "dm4d_arap_fit_rotations")
+    return R, flags
+
+
 class ARAPCoach:
     """``ARAPCoach(verts, faces, device)`` of the reference, mesh (faces given) variant."""
+
+    FLAG_UNCHANGED, FLAG_DET_FLIP = 1, 2      # bits of fit_rotations(..., return_flags=True)
 
     def __init__(self, verts, faces, device):
         self.device = torch.device(device)
@@ -108,13 +132,30 @@ class ARAPCoach:
         self._w, self._e = T(w, torch.float32), T(e, torch.float32)
         self.edge_weights, self.edge_sources, self.edge_targets = w, src, nbr
 
-    def compute_arap_energy(self, xyz_prime, vert_rotations):
+    def fit_rotations(self, xyz_prime, return_flags=False):
+        """The rotations the reference fits when none are given (arap_utils.py:195-214): xyz_prime [V,3] -> R [V,3,3], or batched
+        [T,V,3] -> [T,V,3,3]; float32, detached.  ``return_flags=True`` adds a uint8 tensor [V] / [T,V]: FLAG_UNCHANGED = the
+        reference's "unchanged" rule applied (R = I), FLAG_DET_FLIP = its determinant-flip branch (det of the covariance < 0)."""
+        if not xyz_prime.is_cuda:
+            raise _lib.Dm4dError("ARAP rotation fit runs on the HIP device (no CPU fallback in the product)")
+        single = xyz_prime.dim() == 2
+        x = (xyz_prime[None] if single else xyz_prime).detach().to(torch.float32).contiguous()
+        if x.dim() != 3 or x.shape[1] != self.n_verts or x.shape[2] != 3:
+            raise ValueError(f"xyz_prime must be [{self.n_verts},3] or [T,{self.n_verts},3], got {tuple(xyz_prime.shape)}")
+        R, flags = _fit_rotations(self, x, return_flags)
+        if single:
+            R, flags = R[0], None if flags is None else flags[0]
+        return (R, flags) if return_flags else R
+
+    def compute_arap_energy(self, xyz_prime, vert_rotations=None):
         """xyz_prime [V,3] + vert_rotations [V,3,3] -> scalar (the reference's call), or batched
-        [T,V,3] + [T,V,3,3] -> [T] (all timestamps of an iteration in one launch)."""
-        if vert_rotations is None:
-            raise NotImplementedError("the SVD branch (rotations fitted to the deformation) is not on the dynamic stage's path")
+        [T,V,3] + [T,V,3,3] -> [T] (all timestamps of an iteration in one launch).  ``vert_rotations=None`` (the reference's
+        default): the energy under ``fit_rotations(xyz_prime)``, which are constants of the graph -- the gradient to xyz_prime
+        is still the total one (module docstring)."""
         if not xyz_prime.is_cuda:
             raise _lib.Dm4dError("ARAP energy runs on the HIP device (no CPU fallback in the product)")
+        if vert_rotations is None:
+            vert_rotations = self.fit_rotations(xyz_prime)
         single = xyz_prime.dim() == 2
         x = xyz_prime[None] if single else xyz_prime
         r = vert_rotations[None] if single else vert_rotations

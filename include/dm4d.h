@@ -47,7 +47,8 @@ typedef void *dm4d_stream_t;   /* hipStream_t */
 
 /* ABI version = 100 * major + round.  A binding built against this header checks dm4d_version() == DM4D_ABI_VERSION when it loads the
  * library (dreammesh4d_amd/_lib.py does).  Entry points are never changed in place from round 5 on: a new argument is a new symbol
- * (dm4d_adamw_step beside dm4d_adamw_message, dm4d_normal_consistency_backward_scratch beside dm4d_normal_consistency_backward). */
+ * (dm4d_adamw_step beside dm4d_adamw_message, dm4d_normal_consistency_backward_scratch beside dm4d_normal_consistency_backward).
+ * Additions that change nothing existing keep the number: 107 gained dm4d_arap_fit_rotations after the dm4d_sh_eval_* pair. */
 #define DM4D_ABI_VERSION 107
 int dm4d_version(void);
 const char *dm4d_last_error(void);
@@ -442,6 +443,18 @@ int dm4d_arap_energy_backward(int32_t T, int32_t V, const int32_t *csr_offsets, 
                               const int32_t *reverse_edge, const float *weights, const float *rest_edges,
                               const float *xyz_prime, const float *rotations, const float *g_energy, float *g_xyz,
                               float *g_rotations, dm4d_stream_t stream);
+/* The rotations the reference fits when it is called WITHOUT them (vert_rotations=None, arap_utils.py:195-214): per (timestamp,
+ * vertex) the covariance S = sum_j w_ij e_ij e'_ij^T of the rest and deformed one-ring edges, then R = W U^T of its SVD with the
+ * column of the smallest singular value flipped where det <= 0 -- computed as what both branches amount to, the proper rotation
+ * that maximises tr(R S) (Horn's quaternion form, in double; no SVD, no third singular vector).  A vertex whose deformed edge
+ * components equal the rest ones on at least one coordinate axis (the reference's "unchanged" rule, :201-202) gets R = I.
+ * rotations_out [T,V,3,3] row-major; flags_out [T,V] bytes or NULL: bit 0 = treated as unchanged, bit 1 = det(S) < 0 (the
+ * reference's flip branch).  Same adjacency as above without the reverse-edge index.  Atomic-free, deterministic.  Feeding the
+ * result to dm4d_arap_energy_* gives compute_arap_energy(xyz_prime): R is stationary for the energy, so the backward with
+ * g_rotations = NULL is the whole gradient. */
+int dm4d_arap_fit_rotations(int32_t T, int32_t V, const int32_t *csr_offsets, const int32_t *neighbors, const float *weights,
+                            const float *rest_edges, const float *xyz_prime, float *rotations_out, uint8_t *flags_out,
+                            dm4d_stream_t stream);
 
 /* out = softmax(q k^T * scale) v per (batch, head): the self-attentions of the Zero123 UNet's transformer blocks
  * (extern/ldm_zero123/modules/attention.py:152-194) on the matrix cores.  float16 q, k, v with element (b, token, head, c) at
