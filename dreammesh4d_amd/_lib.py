@@ -248,6 +248,10 @@ _SIGNATURES = {
     "dm4d_mesh_raster": (C.c_int, [C.c_int32] * 4 + [vp] * 6 + [C.c_int32, vp, C.c_size_t, vp, vp, vp, vp]),
     "dm4d_tex_claim_bytes": (C.c_size_t, [C.c_int32]),
     "dm4d_tex_accumulate": (C.c_int, [C.c_int32, vp, vp, C.c_int64, C.c_uint32, vp, C.c_size_t, C.c_int32, vp, vp, vp]),
+    "dm4d_simplify_vertex_keys": (C.c_int, [C.c_int64, vp] + [C.c_double] * 4 + [C.c_int64] * 3 + [vp, vp]),
+    "dm4d_simplify_cluster_average": (C.c_int, [C.c_int64] * 2 + [vp] * 8),
+    "dm4d_simplify_face_remap": (C.c_int, [C.c_int64] * 3 + [vp] * 5),
+    "dm4d_simplify_face_first": (C.c_int, [C.c_int64] + [vp] * 4),
 }
 
 

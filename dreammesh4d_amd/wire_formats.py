@@ -154,6 +154,39 @@ def write_ply(path, verts, faces, colors=None, normals=None):
         fh.write(farr.tobytes())
 
 
+def read_obj_geometry(path):
+    """The geometry of any OBJ: ``v x y z [r g b]`` and ``f`` records whose corners are ``i``, ``i/t``, ``i/t/n`` or ``i//n``
+    (1-based, negative = relative to the vertices read so far; polygons fan-triangulated) -> the keys of ``read_ply``:
+    verts [V,3] float64, faces [F,3] int64, colors [V,3] float64 when EVERY vertex carries one, else None, normals None."""
+    v, c, faces = [], [], []
+    with open(path) as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                v.append([float(x) for x in tok[1:4]])
+                if len(tok) >= 7:
+                    c.append([float(x) for x in tok[4:7]])
+            elif tok[0] == "f":
+                idx = [int(t.split("/")[0]) for t in tok[1:]]
+                idx = [i - 1 if i > 0 else len(v) + i for i in idx]
+                for k in range(1, len(idx) - 1):
+                    faces.append((idx[0], idx[k], idx[k + 1]))
+    return {"verts": np.asarray(v, np.float64).reshape(-1, 3), "faces": np.asarray(faces, np.int64).reshape(-1, 3),
+            "colors": np.asarray(c, np.float64) if v and len(c) == len(v) else None, "normals": None}
+
+
+def read_mesh(path):
+    """``read_ply`` or ``read_obj_geometry`` by the file's extension."""
+    ext = path.lower().rsplit(".", 1)[-1]
+    if ext == "ply":
+        return read_ply(path)
+    if ext == "obj":
+        return read_obj_geometry(path)
+    raise ValueError(f"{path}: only .ply and .obj meshes are read")
+
+
 def vertex_normals(verts, faces):
     """Area-weighted vertex normals (what ``mesh.compute_vertex_normals()`` writes, system/base.py:60)."""
     v = np.asarray(verts, np.float64)

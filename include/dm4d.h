@@ -14,6 +14,7 @@
  *                         C/renderer/diff_sugar_rasterizer_normal.py:117-132,161-170,186-195
  *   dm4d_mark_visible     GaussianRasterizer.markVisible (same package)
  *   dm4d_sh_eval_*        SuGaR.get_points_rgb with sh_levels > 1, C/geometry/sugar.py:640-661 (eval_sh :733-820)
+ *   dm4d_simplify_*       open3d's simplify_vertex_clustering as called by C/scripts/mesh_simplification.py:22-26
  *   dm4d_dist2_knn3       simple_knn._C.distCUDA2 (requirements.txt:50), call site
  *                         C/geometry/gaussian_base.py:435-438
  *   dm4d_skin_*           C/geometry/dynamic_sugar.py:408-465,487-613 (+ C/utils/dual_quaternions.py)
@@ -48,7 +49,8 @@ typedef void *dm4d_stream_t;   /* hipStream_t */
 /* ABI version = 100 * major + round.  A binding built against this header checks dm4d_version() == DM4D_ABI_VERSION when it loads the
  * library (dreammesh4d_amd/_lib.py does).  Entry points are never changed in place from round 5 on: a new argument is a new symbol
  * (dm4d_adamw_step beside dm4d_adamw_message, dm4d_normal_consistency_backward_scratch beside dm4d_normal_consistency_backward).
- * Additions that change nothing existing keep the number: 107 gained dm4d_arap_fit_rotations after the dm4d_sh_eval_* pair. */
+ * Additions that change nothing existing keep the number: 107 gained dm4d_arap_fit_rotations after the dm4d_sh_eval_* pair,
+ * then the four dm4d_simplify_* calls. */
 #define DM4D_ABI_VERSION 107
 int dm4d_version(void);
 const char *dm4d_last_error(void);
@@ -961,6 +963,34 @@ size_t dm4d_tex_claim_bytes(int32_t n_texels);
  * (-1 = skip), sum [n_texels,3], count [n_texels].  epoch: 1, 2, 3, ... one per call of a bake, strictly increasing. */
 int dm4d_tex_accumulate(int32_t n_pixels, const int32_t *texel, const float *rgb, int64_t channel_stride, uint32_t epoch, void *claim,
                         size_t claim_bytes, int32_t n_texels, float *sum, float *count, dm4d_stream_t stream);
+
+/* ------------------------------------------------------------------ mesh simplification by vertex clustering
+ * TriangleMesh.simplify_vertex_clustering(voxel_size, contraction = Average) as called by
+ * C/scripts/mesh_simplification.py:22-26 (open3d, un-vendored), with the order of the result made a function of the input:
+ * output vertex c is the cluster with the c-th smallest cell key, its position the float64 sum of its members in ascending
+ * vertex index, divided by their number in float64 and rounded once to float32; faces keep their input order.  The caller
+ * computes the grid on the host (float64), and does the two stable sorts between the calls (dreammesh4d_amd/mesh_simplify.py).
+ * All counts are at most INT32_MAX; index arrays are int64.  No floating-point atomics: two runs give the same bytes. */
+
+/* keys[v] = (iz * ny + iy) * nx + ix with i = floor((double(verts[v]) - origin) / voxel) per axis, in float64.  verts [V,3].
+ * The grid is validated on the host: voxel > 0 and finite, nx, ny, nz >= 1, nx * ny * nz < 2^62 (DM4D_ERR_UNSUPPORTED). */
+int dm4d_simplify_vertex_keys(int64_t V, const float *verts, double origin_x, double origin_y, double origin_z, double voxel,
+                              int64_t nx, int64_t ny, int64_t nz, int64_t *keys, dm4d_stream_t stream);
+/* order [V]: the vertices in a stable ascending sort of their keys; run_start [C]: the position in `order` where each run of
+ * equal keys begins (ascending; the last run ends at V).  Writes out_verts [C,3], out_colors [C,3] (colors [V,3] and out_colors:
+ * both or neither) and vertex_cluster [V] = the run every vertex belongs to.  Entries of order / run_start outside their range
+ * are skipped, never dereferenced. */
+int dm4d_simplify_cluster_average(int64_t V, int64_t C, const int64_t *order, const int64_t *run_start, const float *verts,
+                                  const float *colors, float *out_verts, float *out_colors, int64_t *vertex_cluster,
+                                  dm4d_stream_t stream);
+/* canon [F,3]: the cluster ids of faces [F,3] rotated (not sorted: orientation is kept) so that the smallest comes first;
+ * (-1, -1, -1) for a face with two corners in one cluster or a vertex index outside [0, V).  key_bc [F] = canon[f][1] * C +
+ * canon[f][2] (-1 for a dropped face): a stable sort by key_bc, then by canon[f][0], orders the triples lexicographically. */
+int dm4d_simplify_face_remap(int64_t F, int64_t V, int64_t C, const int64_t *faces, const int64_t *vertex_cluster, int64_t *canon,
+                             int64_t *key_bc, dm4d_stream_t stream);
+/* perm [F]: the faces in that order (a permutation of 0..F-1; equal triples in input order).  keep [F] (uint8) = 1 for a face
+ * that is not dropped and is the first of its run of equal triples, i.e. the occurrence with the lowest input index; else 0. */
+int dm4d_simplify_face_first(int64_t F, const int64_t *perm, const int64_t *canon, uint8_t *keep, dm4d_stream_t stream);
 
 #ifdef __cplusplus
 }
