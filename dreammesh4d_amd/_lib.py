@@ -161,6 +161,8 @@ _SIGNATURES = {
     "dm4d_dist2_knn3": (C.c_int, [C.c_int32, vp, vp, vp]),
     "dm4d_knn_scratch_bytes": (C.c_size_t, [C.c_int32]),
     "dm4d_dist2_knn3_ws": (C.c_int, [C.c_int32, vp, vp, vp, C.c_size_t, vp]),
+    "dm4d_knn_points_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "dm4d_knn_points": (C.c_int, [C.c_int32] * 3 + [vp, vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp, vp, vp]),
     "dm4d_skin_vertices_forward": (C.c_int, [C.c_int32] * 4 + [vp] * 10),
     "dm4d_skin_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "dm4d_skin_vertices_backward": (C.c_int, [C.c_int32] * 4 + [vp] * 17),

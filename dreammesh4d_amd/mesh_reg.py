@@ -13,8 +13,16 @@ C ABI ``dm4d_arap_energy_*`` / ``dm4d_arap_fit_rotations``):
 
 The static part (one-ring neighbours, the reference's cotangent weights, rest edges) is computed once on the
 host with the reference's arithmetic, quirk included (dense branch of ``produce_cot_weights_nfmt``: the weight of
-the directed edge (f_a, f_b) of a face is assigned 0.5 * cot(angle at f_a) / 4, then W + W^T).  The kNN constructor branch
-(``faces=None``, open3d's KD-tree) is not mirrored.
+the directed edge (f_a, f_b) of a face is assigned 0.5 * cot(angle at f_a) / 4, then W + W^T).
+
+The kNN constructor branch (``faces=None``, arap_utils.py:46-70: open3d's KD-tree) is mirrored for the energy with GIVEN
+rotations: the neighbours of a vertex are its 8 nearest other vertices (``knn.knn_points(v, v, 8, exclude_self=True)``; the
+reference asks the tree for 9 and drops the first, which is the vertex itself unless it has an exact duplicate -- exclusion by
+index is this project's statement of that, and ties go to the lower index where FLANN defines no order), the weights
+``exp(-(d2 - min d2) / max d2)`` over those 8.  A kNN graph is not symmetric and ``k_arap_bwd`` reads the reverse edge of every
+edge, so the CSR holds the union of both directions: where i -> j exists and j -> i does not, j -> i is added with weight 0,
+which contributes exactly 0 to the energy and to both gradients.  The fitted-rotation path on such a coach raises
+``NotImplementedError``: the zero-weight neighbours would take part in the reference's "unchanged vertex" rule.
 """
 import ctypes as C
 
@@ -99,12 +107,18 @@ def _fit_rotations(coach, x, want_flags=False):
 
 
 class ARAPCoach:
-    """``ARAPCoach(verts, faces, device)`` of the reference, mesh (faces given) variant."""
+    """``ARAPCoach(verts, faces, device)`` of the reference: the mesh variant (faces given), or with ``faces=None`` the
+    point-cloud variant on the 8 nearest neighbours of every vertex (module docstring)."""
 
     FLAG_UNCHANGED, FLAG_DET_FLIP = 1, 2      # bits of fit_rotations(..., return_flags=True)
+    KNN_CONNECTIVITY = 8                      # nodes_connectivity of arap_utils.py:53
 
     def __init__(self, verts, faces, device):
         self.device = torch.device(device)
+        self.is_knn = faces is None
+        if self.is_knn:
+            self._init_knn(verts)
+            return
         verts_c = torch.as_tensor(verts, dtype=torch.float32).detach().cpu()
         faces_n = np.asarray(torch.as_tensor(faces).cpu() if torch.is_tensor(faces) else faces)
         self.verts = verts_c.to(self.device)
@@ -132,10 +146,46 @@ class ARAPCoach:
         self._w, self._e = T(w, torch.float32), T(e, torch.float32)
         self.edge_weights, self.edge_sources, self.edge_targets = w, src, nbr
 
+    def _init_knn(self, verts):
+        from .knn import knn_points
+
+        K = self.KNN_CONNECTIVITY
+        verts_c = torch.as_tensor(verts, dtype=torch.float32).detach().cpu().contiguous()
+        if verts_c.dim() != 2 or verts_c.shape[1] != 3:
+            raise ValueError(f"verts must be [V,3], got {tuple(verts_c.shape)}")
+        self.verts = verts_c.to(self.device)
+        self.faces, self.n_faces = None, 0
+        V = self.n_verts = int(verts_c.shape[0])
+        nn = knn_points(self.verts, self.verts, K, exclude_self=True)          # ValueError below 9 vertices
+        idx, d2 = nn.idx.cpu(), nn.dists.cpu()
+        wk = torch.exp(-(d2 - d2.min(dim=1, keepdim=True).values) / d2.max(dim=1, keepdim=True).values)    # float32, as :61
+        self.one_ring_neighbors = {i: row for i, row in enumerate(idx.tolist())}      # the reference's view: 8 each, kNN order
+        self.max_n_neighbors = K
+        # CSR on the union of both directions: the kNN edges of a vertex in kNN order, then the reverse-only ones (weight 0)
+        src, dst = np.repeat(np.arange(V, dtype=np.int64), K), idx.numpy().reshape(-1)
+        lone = ~np.isin(dst * V + src, src * V + dst)                           # i -> j whose j -> i is no kNN edge
+        a_src, a_dst = np.concatenate([src, dst[lone]]), np.concatenate([dst, src[lone]])
+        w = np.concatenate([wk.numpy().reshape(-1), np.zeros(int(lone.sum()), np.float32)]).astype(np.float32)
+        order = np.argsort(a_src, kind="stable")
+        src, nbr, w = a_src[order], a_dst[order], w[order]
+        off = np.zeros(V + 1, np.int64)
+        off[1:] = np.cumsum(np.bincount(src, minlength=V))
+        key = src * V + nbr
+        by_key = np.argsort(key)
+        rev = by_key[np.searchsorted(key[by_key], nbr * V + src)]
+        e = (verts_c[src] - verts_c[nbr]).numpy()
+        T = lambda a, dt: torch.as_tensor(a, dtype=dt, device=self.device).contiguous()
+        self._off, self._nbr, self._rev = T(off, torch.int32), T(nbr, torch.int32), T(rev, torch.int32)
+        self._w, self._e = T(w, torch.float32), T(e, torch.float32)
+        self.edge_weights, self.edge_sources, self.edge_targets = w, src, nbr
+
     def fit_rotations(self, xyz_prime, return_flags=False):
         """The rotations the reference fits when none are given (arap_utils.py:195-214): xyz_prime [V,3] -> R [V,3,3], or batched
         [T,V,3] -> [T,V,3,3]; float32, detached.  ``return_flags=True`` adds a uint8 tensor [V] / [T,V]: FLAG_UNCHANGED = the
         reference's "unchanged" rule applied (R = I), FLAG_DET_FLIP = its determinant-flip branch (det of the covariance < 0)."""
+        if self.is_knn:
+            raise NotImplementedError("ARAPCoach(verts, None, device), the kNN branch: rotations are not fitted (its CSR carries "
+                                      "zero-weight reverse edges the reference's 'unchanged vertex' rule would see); pass vert_rotations")
         if not xyz_prime.is_cuda:
             raise _lib.Dm4dError("ARAP rotation fit runs on the HIP device (no CPU fallback in the product)")
         single = xyz_prime.dim() == 2
@@ -155,7 +205,7 @@ class ARAPCoach:
         if not xyz_prime.is_cuda:
             raise _lib.Dm4dError("ARAP energy runs on the HIP device (no CPU fallback in the product)")
         if vert_rotations is None:
-            vert_rotations = self.fit_rotations(xyz_prime)
+            vert_rotations = self.fit_rotations(xyz_prime)      # NotImplementedError on a kNN coach
         single = xyz_prime.dim() == 2
         x = xyz_prime[None] if single else xyz_prime
         r = vert_rotations[None] if single else vert_rotations

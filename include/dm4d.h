@@ -17,6 +17,7 @@
  *   dm4d_simplify_*       open3d's simplify_vertex_clustering as called by C/scripts/mesh_simplification.py:22-26
  *   dm4d_dist2_knn3       simple_knn._C.distCUDA2 (requirements.txt:50), call site
  *                         C/geometry/gaussian_base.py:435-438
+ *   dm4d_knn_points       pytorch3d.ops.knn_points / open3d's KDTreeFlann.search_knn_vector_3d (call sites at its declaration)
  *   dm4d_skin_*           C/geometry/dynamic_sugar.py:408-465,487-613 (+ C/utils/dual_quaternions.py)
  *   dm4d_face_gaussians_* C/geometry/dynamic_sugar.py:657-706,726-743,877-889,330-364 and
  *                         C/geometry/sugar.py:479-518
@@ -50,7 +51,8 @@ typedef void *dm4d_stream_t;   /* hipStream_t */
  * library (dreammesh4d_amd/_lib.py does).  Entry points are never changed in place from round 5 on: a new argument is a new symbol
  * (dm4d_adamw_step beside dm4d_adamw_message, dm4d_normal_consistency_backward_scratch beside dm4d_normal_consistency_backward).
  * Additions that change nothing existing keep the number: 107 gained dm4d_arap_fit_rotations after the dm4d_sh_eval_* pair,
- * then the four dm4d_simplify_* calls. */
+ * then the four dm4d_simplify_* calls,
+ * then dm4d_knn_points and its scratch size. */
 #define DM4D_ABI_VERSION 107
 int dm4d_version(void);
 const char *dm4d_last_error(void);
@@ -287,6 +289,24 @@ int dm4d_dist2_knn3(int32_t N, const float *points, float *out, dm4d_stream_t st
  * dm4d_knn_scratch_bytes(N) bytes, 256-byte aligned, uninitialised. */
 size_t dm4d_knn_scratch_bytes(int32_t N);
 int dm4d_dist2_knn3_ws(int32_t N, const float *points, float *out, void *scratch, size_t scratch_bytes, dm4d_stream_t stream);
+
+/* pytorch3d.ops.knn_points (C/geometry/sugar.py:636, C/system/base.py:349, C/utils/sugar_utils.py) and open3d's
+ * KDTreeFlann.search_knn_vector_3d (C/utils/arap_utils.py:46-70, C/geometry/dynamic_sugar.py:762-812): for every query the K
+ * nearest of `points`, squared distances and indices.  Exact, and unique:
+ *   d2 = (dx*dx + dy*dy) + dz*dz in float32 with dx = q.x - p.x, no FMA contraction (dm4d_dist2_knn3's form);
+ *   a query's K results are the K smallest under the lexicographic order (d2, point index), written ascending in that
+ *   order -- ties go to the lower index (pytorch3d and FLANN define no tie order);
+ *   exclude_same_index != 0 skips candidate j for query i when j == i (the search of a cloud in itself; a duplicate of a point
+ *   still counts).
+ * 1 <= K <= 32 and K <= the number of candidates (Np, or Np - 1 with exclusion), else DM4D_ERR_INVALID and nothing is launched
+ * or written.  method 0: LDS-tiled exhaustive search, no scratch.  method 1: dm4d_dist2_knn3_ws's Morton-ordered boxes over
+ * `points`, the queries sorted by the same key (`query == points` with Nq == Np reuses the one order); `scratch` [dev]:
+ * dm4d_knn_points_scratch_bytes(Nq, Np, K, 1) bytes, 256-byte aligned, uninitialised.  Both methods return identical bytes.
+ * query [dev] [Nq,3], points [dev] [Np,3], dist2 [dev] [Nq,K], idx [dev] [Nq,K].  Every index written lies in [0, Np), also for
+ * non-finite coordinates (the values of such rows are unspecified). */
+size_t dm4d_knn_points_scratch_bytes(int32_t Nq, int32_t Np, int32_t K, int32_t method);
+int dm4d_knn_points(int32_t Nq, int32_t Np, int32_t K, const float *query, const float *points, int32_t exclude_same_index,
+                    int32_t method, void *scratch, size_t scratch_bytes, float *dist2, int32_t *idx, dm4d_stream_t stream);
 
 /* ------------------------------------------------------------------ skinning / face -> Gaussians */
 
