@@ -6,265 +6,129 @@ infrastructure and are never imported from here.)
 """
 import ctypes as C
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libdm4d_hip.so")
 _LIB = None
 
-OK = 0
 c_f = C.POINTER(C.c_float)
 c_i32 = C.POINTER(C.c_int32)
 c_u32 = C.POINTER(C.c_uint32)
 c_u64 = C.POINTER(C.c_uint64)
 c_u8 = C.POINTER(C.c_uint8)
-vp = C.c_void_p
 
 
 class Dm4dError(RuntimeError):
     pass
 
 
-class RasterSettings(C.Structure):
-    _fields_ = [
-        ("image_height", C.c_int32), ("image_width", C.c_int32), ("tanfovx", C.c_float), ("tanfovy", C.c_float),
-        ("scale_modifier", C.c_float), ("sh_degree", C.c_int32), ("prefiltered", C.c_int32), ("debug", C.c_int32),
-        ("bg", vp), ("viewmatrix", vp), ("projmatrix", vp), ("campos", vp),
-    ]
-
-
-class RasterInputs(C.Structure):
-    _fields_ = [
-        ("N", C.c_int32), ("sh_coeffs", C.c_int32), ("n_channels", C.c_int32), ("means3D", vp), ("shs", vp), ("colors_precomp", vp),
-        ("opacities", vp), ("scales", vp), ("rotations", vp), ("cov3D_precomp", vp),
-    ]
-
-
-class ViewsStruct(C.Structure):
-    """dm4d_views (include/dm4d.h)."""
-    _fields_ = [(n, C.c_int32) for n in ("B", "N", "F", "G", "V", "M", "K", "method", "image_height", "image_width")] + \
-               [(n, C.c_float) for n in ("tanfovx", "tanfovy", "scale_modifier")] + [("capacity", C.c_int64), ("record_capacity", C.c_int64)] + \
-               [(n, vp) for n in ("bg", "viewmatrix", "projmatrix", "verts", "nbr_idx", "nbr_w", "dx", "dr", "ds",
-                                  "d_opacity", "faces", "q_static", "scales", "opacities", "rgb", "vxyz", "vrot",
-                                  "means3D", "rotations", "colors", "radii", "out_color", "out_depth", "out_alpha",
-                                  "geom", "binning", "image", "frame_index")] + [("n_frames", C.c_int32), ("scales_per_frame", C.c_int32), ("record_mode", C.c_int32)]
-
-
-class ViewsGrads(C.Structure):
-    """dm4d_views_grads (include/dm4d.h)."""
-    _fields_ = [(n, vp) for n in ("dL_dcolor", "dL_ddepth", "dL_dalpha", "dL_dvxyz_ext", "dL_dvrot_ext",
-                                  "node_csr_offsets", "node_csr_items", "vert_csr_offsets", "vert_csr_items",
-                                  "grad_scratch", "skin_scratch", "face_scratch", "dL_dmeans2D", "dL_dmeans3D",
-                                  "dL_drotations", "dL_dcolors", "dL_dopacity", "dL_dscales", "dL_dvxyz", "dL_dvrot",
-                                  "dL_ddx", "dL_ddr", "dL_dds", "dL_ddo")]
-
-
-class GViewsStruct(C.Structure):
-    """dm4d_gviews (include/dm4d.h)."""
-    _fields_ = [(n, C.c_int32) for n in ("B", "N", "image_height", "image_width")] + \
-               [(n, C.c_float) for n in ("tanfovx", "tanfovy", "scale_modifier")] + [("record_mode", C.c_int32), ("capacity", C.c_int64), ("record_capacity", C.c_int64)] + \
-               [(n, vp) for n in ("bg", "viewmatrix", "projmatrix", "means3D", "rotations", "scales", "opacities", "colors", "radii",
-                                  "out_color", "out_depth", "out_alpha", "geom", "binning", "image")]
-
-
-class GViewsGrads(C.Structure):
-    """dm4d_gviews_grads (include/dm4d.h)."""
-    _fields_ = [(n, vp) for n in ("dL_dcolor", "dL_ddepth", "dL_dalpha", "grad_scratch", "dL_dmeans2D", "dL_dmeans3D", "dL_drotations",
-                                  "dL_dscales", "dL_dopacity", "dL_dcolors")]
-
-
-class MlpWeights(C.Structure):
-    """dm4d_mlp_weights (include/dm4d.h)."""
-    _fields_ = [("in_dim", C.c_int32), ("width", C.c_int32), ("n_heads", C.c_int32), ("out_dim", C.c_int32 * 4),
-                ("W0", vp), ("b0", vp), ("W1", vp * 4), ("b1", vp * 4), ("W2", vp * 4), ("b2", vp * 4)]
-
-
-class MlpWeightsGrad(C.Structure):
-    """dm4d_mlp_weights_grad (include/dm4d.h)."""
-    _fields_ = [("W0", vp), ("b0", vp), ("W1", vp * 4), ("b1", vp * 4), ("W2", vp * 4), ("b2", vp * 4)]
-
-
-class StepDesc(C.Structure):
-    """dm4d_step_desc (include/dm4d.h)."""
-    _fields_ = [("views", ViewsStruct), ("grads", ViewsGrads), ("S", C.c_int32), ("hex_flags", C.c_int32), ("hex_backward_flags", C.c_int32),
-                ("res", vp), ("aabb_host", vp), ("planes", vp), ("g_planes", vp), ("nodes", vp), ("times", vp),
-                ("w", MlpWeights), ("gw", MlpWeightsGrad), ("node_out", vp * 4), ("node_gout", vp * 4),
-                ("feat", vp), ("h_save", vp), ("y_save", vp), ("g_feat", vp), ("samples", vp), ("net_scratch", vp),
-                ("n_spatial", C.c_int32), ("n_time", C.c_int32)] + \
-               [(n, vp) for n in ("sp_scale", "sp_plane", "sp_texel", "sp_off", "sp_item", "tp_scale", "tp_plane", "tp_col", "tp_off", "tp_item")]
-
-
-MAX_GRAD_SEGMENTS = 64
-
-
-class GradSegments(C.Structure):
-    """dm4d_grad_segments (include/dm4d.h)."""
-    _fields_ = [("n_segments", C.c_int32), ("grad", vp * MAX_GRAD_SEGMENTS), ("index", vp * MAX_GRAD_SEGMENTS),
-                ("count", C.c_int64 * MAX_GRAD_SEGMENTS), ("offset", C.c_int64 * MAX_GRAD_SEGMENTS)]
-
-
-class AdamwArgs(C.Structure):
-    """dm4d_adamw_args (include/dm4d.h)."""
-    _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("n_groups", C.c_int32),
-                ("lr", C.c_float * 8), ("group", C.c_int32 * MAX_GRAD_SEGMENTS), ("param", vp * MAX_GRAD_SEGMENTS), ("exp_avg", vp),
-                ("exp_avg_sq", vp), ("step", vp), ("pending_decay", vp), ("found_inf", vp), ("scratch", vp)]
-
-
-class AdamwStepArgs(C.Structure):
-    """dm4d_adamw_step_args (include/dm4d.h)."""
-    _fields_ = [("n_groups", C.c_int32), ("lr", C.c_float * 8), ("beta1", C.c_float * 8), ("beta2", C.c_float * 8), ("eps", C.c_float * 8),
-                ("weight_decay", C.c_float * 8), ("group", C.c_int32 * MAX_GRAD_SEGMENTS), ("param", vp * MAX_GRAD_SEGMENTS),
-                ("param_out", vp * MAX_GRAD_SEGMENTS), ("grad_in_message", C.c_uint8 * MAX_GRAD_SEGMENTS), ("skip", C.c_uint8 * MAX_GRAD_SEGMENTS),
-                ("exp_avg", vp), ("exp_avg_sq", vp), ("step", vp), ("pending_decay", vp), ("found_inf", vp), ("scratch", vp)]
-
-
+# the one function-pointer typedef of the header; the parser refuses any other
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, C.c_size_t)
 
-_SIGNATURES = {
-    "dm4d_version": (C.c_int, []),
-    "dm4d_last_error": (C.c_char_p, []),
-    "dm4d_device_count": (C.c_int, []),
-    "dm4d_profile_enable": (None, [C.c_uint]),
-    "dm4d_profile_collect": (C.c_int64, [C.c_int, C.POINTER(C.c_double)]),
-    "dm4d_device_arch": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
-    "dm4d_raster_geom_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
-    "dm4d_raster_binning_bytes": (C.c_size_t, [C.c_int64]),
-    "dm4d_raster_image_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
-    "dm4d_raster_grad_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
-    "dm4d_rasterize_prepare": (C.c_int, [C.POINTER(RasterSettings), C.POINTER(RasterInputs), vp, vp, C.c_size_t, vp]),
-    "dm4d_rasterize_num_rendered": (C.c_int64, [vp, vp]),
-    "dm4d_rasterize_num_records": (C.c_int64, [vp, vp]),
-    "dm4d_rasterize_counts": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
-    "dm4d_rasterize_render": (C.c_int, [C.POINTER(RasterSettings), C.POINTER(RasterInputs), vp, vp, vp, C.c_int64,
-                                        vp, vp, vp, vp, vp]),
-    "dm4d_rasterize_overflowed": (C.c_int, [vp, vp]),
-    "dm4d_rasterize_backward": (C.c_int, [C.POINTER(RasterSettings), C.POINTER(RasterInputs), vp, vp, vp, C.c_int64,
-                                          vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "dm4d_rasterize_forward": (C.c_int64, [C.POINTER(RasterSettings), C.POINTER(RasterInputs), vp, vp, vp, vp,
-                                           ALLOC_FN, vp, vp]),
-    "dm4d_raster_read_sorted": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, c_u64, c_u32, c_u32, vp]),
-    "dm4d_raster_read_geom": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, c_f, c_f, c_f, c_u32, vp]),
-    "dm4d_raster_read_image_state": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, c_u32, c_f, vp]),
-    "dm4d_debug_trace": (C.c_int, [vp, C.c_uint32]),
-    "dm4d_debug_sort_trace": (C.c_int, [vp]),
-    "dm4d_mark_visible": (C.c_int, [C.c_int32, vp, vp, vp, vp]),
-    "dm4d_sh_eval_forward": (C.c_int, [C.c_int32] * 3 + [vp] * 6),
-    "dm4d_sh_eval_backward": (C.c_int, [C.c_int32] * 3 + [vp] * 8),
-    "dm4d_groupnorm_nhwc_forward": (C.c_int, [C.c_int32] * 5 + [vp, vp, C.c_int32, vp, vp, C.c_float, C.c_int32, vp, vp, vp, C.c_int32, vp]),
-    "dm4d_groupnorm_nhwc_backward": (C.c_int, [C.c_int32] * 5 + [vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp]),
-    "dm4d_sds_prepare": (C.c_int, [C.c_int32] * 3 + [C.c_float] + [vp] * 17),
-    "dm4d_sds_finish": (C.c_int, [C.c_int32] * 3 + [C.c_float, C.c_float] + [vp] * 18),
-    "dm4d_groupnorm_nhwc_backward_add": (C.c_int, [C.c_int32] * 5 + [vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp]),
-    "dm4d_add_bias_nhwc": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]),
-    "dm4d_geglu": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]),
-    "dm4d_add_layernorm_f16": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp]),
-    "dm4d_dist2_knn3": (C.c_int, [C.c_int32, vp, vp, vp]),
-    "dm4d_knn_scratch_bytes": (C.c_size_t, [C.c_int32]),
-    "dm4d_dist2_knn3_ws": (C.c_int, [C.c_int32, vp, vp, vp, C.c_size_t, vp]),
-    "dm4d_knn_points_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
-    "dm4d_knn_points": (C.c_int, [C.c_int32] * 3 + [vp, vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp, vp, vp]),
-    "dm4d_skin_vertices_forward": (C.c_int, [C.c_int32] * 4 + [vp] * 10),
-    "dm4d_skin_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
-    "dm4d_skin_vertices_backward": (C.c_int, [C.c_int32] * 4 + [vp] * 17),
-    "dm4d_vertex_scales_forward": (C.c_int, [C.c_int32] * 5 + [vp] * 6),
-    "dm4d_vertex_scales_backward": (C.c_int, [C.c_int32] * 5 + [vp] * 10),
-    "dm4d_gaussian_scales_forward": (C.c_int, [C.c_int32] * 4 + [vp] * 6),
-    "dm4d_gaussian_scales_backward": (C.c_int, [C.c_int32] * 4 + [vp] * 10),
-    "dm4d_face_gaussians_forward": (C.c_int, [C.c_int32] * 2 + [vp] * 8),
-    "dm4d_face_scratch_bytes": (C.c_size_t, [C.c_int32]),
-    "dm4d_face_gaussians_backward": (C.c_int, [C.c_int32] * 3 + [vp] * 13),
-    "dm4d_graph_geodesic_scratch_bytes": (C.c_size_t, [C.c_int32] * 2),
-    "dm4d_graph_geodesic_knn": (C.c_int, [C.c_int32] * 3 + [vp] * 10),
-    "dm4d_laplacian_smoothing_forward": (C.c_int, [C.c_int32] * 2 + [vp] * 6),
-    "dm4d_laplacian_smoothing_backward": (C.c_int, [C.c_int32] * 2 + [vp] * 6),
-    "dm4d_normal_consistency_forward": (C.c_int, [C.c_int32] * 3 + [vp] * 4),
-    "dm4d_normal_consistency_backward": (C.c_int, [C.c_int32] * 3 + [vp] * 7),
-    "dm4d_normal_consistency_backward_scratch": (C.c_int, [C.c_int32] * 3 + [vp] * 8),
-    "dm4d_hexplane_forward": (C.c_int, [C.c_int32] * 3 + [vp] * 2 + [C.c_int32] + [vp] * 6),
-    "dm4d_hexplane_axis_index": (C.c_int, [C.c_int32] * 2 + [vp] * 5),
-    "dm4d_hexplane_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
-    "dm4d_hexplane_backward": (C.c_int, [C.c_int32] * 3 + [vp] * 2 + [C.c_int32] + [vp] * 4 + [C.c_int32] + [vp] * 5 + [C.c_int32] + [vp] * 8),
-    "dm4d_conv3x3_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
-    "dm4d_conv3x3_nhwc_f16": (C.c_int, [C.c_int32] * 5 + [vp] * 7),
-    "dm4d_conv3x3_c128_small_nhwc_f16": (C.c_int, [C.c_int32] * 4 + [vp] * 4),
-    "dm4d_conv3x3_strided_scratch_bytes": (C.c_size_t, [C.c_int32] * 6),
-    "dm4d_conv3x3_strided_nhwc_f16": (C.c_int, [C.c_int32] * 7 + [vp] * 7),
-    "dm4d_conv3x3_s2_dgrad_nhwc_f16": (C.c_int, [C.c_int32] * 5 + [vp, C.POINTER(C.c_void_p), vp, vp]),
-    "dm4d_attention_f16": (C.c_int, [C.c_int32] * 4 + [vp] * 3 + [C.c_int64, C.c_int64, vp, C.c_float, vp]),
-    "dm4d_image_head_blocks": (C.c_int32, [C.c_int32, C.c_int32]),
-    "dm4d_image_head_forward": (C.c_int, [C.c_int32] * 4 + [vp] * 7 + [C.c_int32, C.c_int32, vp, vp, vp]),
-    "dm4d_image_head_backward": (C.c_int, [C.c_int32] * 4 + [vp] * 7 + [C.c_int32, C.c_int32] + [vp] * 6),
-    "dm4d_partial_sums": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, vp, C.POINTER(C.c_float), vp, vp]),
-    "dm4d_weighted_sum": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_float), vp, vp]),
-    "dm4d_weighted_sum_backward": (C.c_int, [C.c_int32, vp, C.POINTER(C.c_float), vp, vp]),
-    "dm4d_static_head_blocks": (C.c_int32, [C.c_int32, C.c_int32]),
-    "dm4d_static_head_forward": (C.c_int, [C.c_int32] * 3 + [vp] * 8 + [C.c_int32, C.c_int32, vp, vp, vp]),
-    "dm4d_static_head_backward": (C.c_int, [C.c_int32] * 3 + [vp] * 8 + [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]),
-    "dm4d_sugar_attributes_forward": (C.c_int, [C.c_int32] * 3 + [vp] * 7 + [C.c_float, C.c_float] + [vp] * 6),
-    "dm4d_sugar_attributes_backward": (C.c_int, [C.c_int32] * 3 + [vp] * 7 + [C.c_float, C.c_float] + [vp] * 13),
-    "dm4d_quat_to_matrix_forward": (C.c_int, [C.c_int64, vp, vp, vp]),
-    "dm4d_quat_to_matrix_backward_pypose": (C.c_int, [C.c_int64, vp, vp, vp, vp]),
-    "dm4d_linear_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
-    "dm4d_linear_f16": (C.c_int, [C.c_int64, C.c_int32, C.c_int32] + [vp] * 5 + [C.c_int32, vp, vp]),
-    "dm4d_cg_batched_scratch_bytes": (C.c_size_t, [C.c_int32] * 2),
-    "dm4d_cg_batched_f64": (C.c_int, [C.c_int32] * 2 + [vp] * 7 + [C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_double), vp]),
-    "dm4d_heat_face_directions": (C.c_int, [C.c_int32] * 2 + [vp] * 5),
-    "dm4d_graph_select_knn": (C.c_int, [C.c_int32] * 3 + [vp, C.c_int32, C.c_int32] + [vp] * 5),
-    "dm4d_nodenet_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
-    "dm4d_nodenet_forward": (C.c_int, [C.c_int32] * 3 + [vp] * 2 + [C.c_int32] + [vp] * 3 + [C.POINTER(MlpWeights)] + [vp] * 4 + [C.POINTER(vp)] + [vp] * 2),
-    "dm4d_nodenet_backward": (C.c_int, [C.c_int32] * 3 + [vp] * 2 + [C.c_int32] + [vp] * 3 + [C.POINTER(MlpWeights)] + [vp] * 4 + [C.POINTER(vp)]
-                              + [C.c_int32] + [vp] * 5 + [C.c_int32] + [vp] * 5 + [vp] * 2 + [C.POINTER(MlpWeightsGrad)] + [vp] * 2),
-    "dm4d_deform_mlp_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
-    "dm4d_deform_mlp_forward": (C.c_int, [C.c_int32, vp, C.POINTER(MlpWeights), vp, vp, C.POINTER(vp), vp, vp]),
-    "dm4d_deform_mlp_backward": (C.c_int, [C.c_int32, vp, C.POINTER(MlpWeights), vp, vp, C.POINTER(vp), vp,
-                                           C.POINTER(MlpWeightsGrad), vp, vp]),
-    "dm4d_arap_energy_forward": (C.c_int, [C.c_int32, C.c_int32] + [vp] * 9),
-    "dm4d_arap_energy_backward": (C.c_int, [C.c_int32, C.c_int32] + [vp] * 11),
-    "dm4d_arap_fit_rotations": (C.c_int, [C.c_int32, C.c_int32] + [vp] * 8),
-    "dm4d_grad_pack": (C.c_int, [C.POINTER(GradSegments), vp, vp]),
-    "dm4d_grad_unpack": (C.c_int, [C.POINTER(GradSegments), vp, C.c_float, vp]),
-    "dm4d_adamw_message": (C.c_int, [C.POINTER(GradSegments), C.POINTER(AdamwArgs), C.c_float, vp]),
-    "dm4d_adamw_step": (C.c_int, [C.POINTER(GradSegments), C.POINTER(AdamwStepArgs), C.c_float, vp]),
-    "dm4d_views_geom_bytes": (C.c_size_t, [C.c_int32] * 4),
-    "dm4d_views_binning_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
-    "dm4d_views_image_bytes": (C.c_size_t, [C.c_int32] * 3),
-    "dm4d_views_grad_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
-    "dm4d_views_skin_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
-    "dm4d_views_face_scratch_bytes": (C.c_size_t, [C.c_int32] * 2),
-    "dm4d_views_forward": (C.c_int, [C.POINTER(ViewsStruct), vp]),
-    "dm4d_gviews_forward": (C.c_int, [C.POINTER(GViewsStruct), vp]),
-    "dm4d_gviews_backward": (C.c_int, [C.POINTER(GViewsStruct), C.POINTER(GViewsGrads), vp]),
-    "dm4d_views_backward": (C.c_int, [C.POINTER(ViewsStruct), C.POINTER(ViewsGrads), vp]),
-    "dm4d_views_backward_rgb": (C.c_int, [C.POINTER(ViewsStruct), C.POINTER(ViewsGrads), vp]),
-    "dm4d_views_counters": (C.c_int, [C.POINTER(ViewsStruct), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
-                                      C.POINTER(C.c_int32), vp]),
-    "dm4d_step_create": (C.c_int, [C.POINTER(StepDesc), C.POINTER(vp)]),
-    "dm4d_step_destroy": (None, [vp]),
-    "dm4d_step_forward": (C.c_int, [vp] * 6),
-    "dm4d_step_backward": (C.c_int, [vp] * 7),
-    "dm4d_step_backward_rgb": (C.c_int, [vp] * 6),
-    "dm4d_step_views": (vp, [vp]),
-    "dm4d_tex_atlas_size": (C.c_int32, [C.c_int32, C.c_int32]),
-    "dm4d_tex_atlas_init": (C.c_int, [C.c_int32] * 3 + [vp] * 8),
-    "dm4d_mesh_raster_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
-    "dm4d_mesh_raster": (C.c_int, [C.c_int32] * 4 + [vp] * 6 + [C.c_int32, vp, C.c_size_t, vp, vp, vp, vp]),
-    "dm4d_tex_claim_bytes": (C.c_size_t, [C.c_int32]),
-    "dm4d_tex_accumulate": (C.c_int, [C.c_int32, vp, vp, C.c_int64, C.c_uint32, vp, C.c_size_t, C.c_int32, vp, vp, vp]),
-    "dm4d_simplify_vertex_keys": (C.c_int, [C.c_int64, vp] + [C.c_double] * 4 + [C.c_int64] * 3 + [vp, vp]),
-    "dm4d_simplify_cluster_average": (C.c_int, [C.c_int64] * 2 + [vp] * 8),
-    "dm4d_simplify_face_remap": (C.c_int, [C.c_int64] * 3 + [vp] * 5),
-    "dm4d_simplify_face_first": (C.c_int, [C.c_int64] + [vp] * 4),
-}
+_SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "char": C.c_char, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+            "int32_t": C.c_int32, "int64_t": C.c_int64, "uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
+_DECLARATOR = re.compile(r"(?:(?P<type>\w[\w\s]*?)(?=[\s*])\s*)?(?P<stars>(?:\*\s*(?:const\b\s*)?)*)(?P<name>\w+)(?:\[(?P<bound>\w+)\])?")
+
+
+def parse_header(text, fn_typedefs=None):
+    """(constants, structs, signatures) of a C header written the way include/dm4d.h is: `#define NAME <integer>`, `typedef struct
+    tag { fields } name;` and `ret name(args);`.  constants: name -> int.  structs: C name -> ctypes.Structure, fields in
+    declaration order (fixed-width scalars, c_void_p for every pointer, `type * N` for arrays, earlier structs by value).
+    signatures: name -> (restype, argtypes); an argument that points to one of the structs is POINTER(struct), a function-pointer
+    typedef is looked up in `fn_typedefs`, every other pointer is c_void_p (device pointers arrive as ints), a returned pointer is
+    c_void_p too, or c_char_p for `char *`.  Anything else raises ValueError naming the text: nothing is skipped."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif\b[^\n]*", "", text, flags=re.S | re.M)   # C, not C++
+    constants, structs, signatures = {}, {}, {}
+    known = dict(_SCALARS, void=None)       # every type name a declaration may use -> what it is by value (None: only behind a pointer)
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(\S[^\n]*?)[ \t]*$", text, flags=re.M):
+        try:
+            constants[name] = int(value, 0)
+        except ValueError:
+            raise ValueError(f"#define {name} {value}: not an integer literal") from None
+    text = re.sub(r"^[ \t]*#[^\n]*", "", text, flags=re.M)
+
+    def declarator(decl, base=None, struct_pointers=False):
+        """ctype and name of `[type] [*...] name [[N]]`; `base` is the type of a second declarator (`float *a, *b`)."""
+        m = _DECLARATOR.fullmatch(decl.strip())
+        words = [w for w in ((m and m["type"]) or base or "").split() if w not in ("const", "struct")]
+        if not m or (m["type"] and base) or len(words) != 1:
+            raise ValueError(f"cannot parse declaration '{decl.strip()}'")
+        if words[0] not in known:
+            raise ValueError(f"unknown type '{words[0]}' in '{decl.strip()}'")
+        stars, t = m["stars"].count("*"), known[words[0]]
+        if stars:
+            t = C.POINTER(t) if struct_pointers and stars == 1 and words[0] in structs else C.c_void_p
+        elif t is None:
+            raise ValueError(f"'{words[0]}' by value in '{decl.strip()}'")
+        if m["bound"]:
+            if not m["bound"].isdigit() and m["bound"] not in constants:
+                raise ValueError(f"unknown array bound '{m['bound']}' in '{decl.strip()}'")
+            t = t * (int(m["bound"]) if m["bound"].isdigit() else constants[m["bound"]])
+        return t, m["name"], m["type"] or base
+
+    depth, begin, statements = 0, 0, []
+    for i, ch in enumerate(text):
+        depth += (ch == "{") - (ch == "}")
+        if ch == ";" and depth == 0:
+            statements.append(" ".join(text[begin:i].split()))
+            begin = i + 1
+    if depth or text[begin:].strip():
+        raise ValueError(f"cannot parse declaration '{' '.join(text[begin:].split())[:200]}'")
+
+    for st in statements:
+        if m := re.fullmatch(r"typedef struct (\w+) \{(.*)\} (\w+)", st):
+            fields = []
+            for field in filter(None, (f.strip() for f in m[2].split(";"))):
+                base = None
+                for decl in field.split(","):
+                    t, name, base = declarator(decl, base)
+                    fields.append((name, t))
+            known[m[3]] = structs[m[3]] = type(m[3], (C.Structure,), {"_fields_": fields, "__doc__": f"{m[3]} (include/dm4d.h)."})
+        elif m := re.fullmatch(r"typedef struct (\w+) (\w+)", st):          # opaque handle: only ever behind a pointer
+            known[m[2]] = None
+        elif m := re.fullmatch(r"typedef [^()]*\(\s*\*\s*(\w+)\s*\)\s*\(.*\)", st):
+            if m[1] not in (fn_typedefs or {}):
+                raise ValueError(f"unknown function-pointer typedef '{m[1]}' in '{st}'")
+            known[m[1]] = fn_typedefs[m[1]]
+        elif st.startswith("typedef "):
+            t, name, _ = declarator(st[len("typedef "):])
+            known[name] = t
+        elif m := re.fullmatch(r"([\w\s*]+?)\b(\w+) ?\((.*)\)", st):
+            ret = m[1].replace("const", " ").replace("*", " * ").split()
+            if not ret or ret[0] not in known or ret[1:] != ["*"] * (len(ret) - 1):
+                raise ValueError(f"unknown return type '{m[1].strip()}' in '{st}'")
+            res = (C.c_char_p if ret[0] == "char" else C.c_void_p) if len(ret) > 1 else known[ret[0]]
+            args = [] if m[3].strip() == "void" else [declarator(a, struct_pointers=True)[0] for a in m[3].split(",")]
+            signatures[m[2]] = (res, args)
+        else:
+            raise ValueError(f"cannot parse declaration '{st}'")
+    return constants, structs, signatures
+
+
+with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d.h")) as _f:
+    _CONSTANTS, _STRUCTS, _SIGNATURES = parse_header(_f.read(), {"dm4d_alloc_fn": ALLOC_FN})
+globals().update(_CONSTANTS)            # _lib.DM4D_ERR_INVALID, _lib.DM4D_GRAD_PYPOSE, ...
+OK = _CONSTANTS["DM4D_OK"]
+MAX_GRAD_SEGMENTS = _CONSTANTS["DM4D_MAX_GRAD_SEGMENTS"]
+RasterSettings, RasterInputs = _STRUCTS["dm4d_raster_settings"], _STRUCTS["dm4d_raster_inputs"]
+ViewsStruct, ViewsGrads = _STRUCTS["dm4d_views"], _STRUCTS["dm4d_views_grads"]
+GViewsStruct, GViewsGrads = _STRUCTS["dm4d_gviews"], _STRUCTS["dm4d_gviews_grads"]
+MlpWeights, MlpWeightsGrad = _STRUCTS["dm4d_mlp_weights"], _STRUCTS["dm4d_mlp_weights_grad"]
+StepDesc = _STRUCTS["dm4d_step_desc"]
+GradSegments, AdamwArgs, AdamwStepArgs = _STRUCTS["dm4d_grad_segments"], _STRUCTS["dm4d_adamw_args"], _STRUCTS["dm4d_adamw_step_args"]
 
 
 def declared_symbols():
-    """Every function include/dm4d.h declares (parsed from the header, not from this table)."""
-    import re
+    """Every function include/dm4d.h declares."""
+    return sorted(_SIGNATURES)
 
-    hdr = os.path.join(os.path.dirname(_HERE), "include", "dm4d.h")
-    text = open(hdr).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(dm4d_[a-z0-9_]+)\s*\(", text)) - {"dm4d_alloc_fn"})
+
+def abi_version() -> int:
+    """DM4D_ABI_VERSION of include/dm4d.h (the header the binding is derived from)."""
+    return _CONSTANTS["DM4D_ABI_VERSION"]
 
 
 def build(force: bool = False) -> str:
@@ -297,16 +161,24 @@ def lib() -> C.CDLL:
     return _LIB
 
 
-def abi_version() -> int:
-    """DM4D_ABI_VERSION of include/dm4d.h (the header this table of signatures was written against)."""
-    import re
-
-    hdr = os.path.join(os.path.dirname(_HERE), "include", "dm4d.h")
-    return int(re.search(r"#define\s+DM4D_ABI_VERSION\s+(\d+)", open(hdr).read()).group(1))
-
-
 def check(rc, what=""):
     if rc is not None and rc < 0:
         msg = lib().dm4d_last_error()
         raise Dm4dError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
     return rc
+
+
+def call(name, *args):
+    """Call entry point `name` and raise Dm4dError (with the name and the library's message) on a negative return."""
+    return check(getattr(lib(), name)(*args), name)
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def stream(dev):
+    """Handle of torch's current stream on `dev`."""
+    import torch
+
+    return torch.cuda.current_stream(dev).cuda_stream

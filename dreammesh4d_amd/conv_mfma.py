@@ -50,10 +50,9 @@ def conv3x3(x, w_ohwi, bias=None, residual=None, stride=1, pad=1):
     # gets it from the graph's own pool)
     buf = torch.empty(L.dm4d_conv3x3_strided_scratch_bytes(N, Hin, Win, Ci, Co, stride), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(L.dm4d_conv3x3_strided_nhwc_f16(N, Hin, Win, Ci, Co, stride, pad, x.data_ptr(), w_ohwi.data_ptr(),
-                                                   0 if bias is None else bias.data_ptr(), 0 if residual is None else residual.data_ptr(),
-                                                   y.data_ptr(), buf.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream),
-                   "dm4d_conv3x3_strided_nhwc_f16")
+        _lib.call("dm4d_conv3x3_strided_nhwc_f16", N, Hin, Win, Ci, Co, stride, pad, x.data_ptr(), w_ohwi.data_ptr(),
+                  0 if bias is None else bias.data_ptr(), 0 if residual is None else residual.data_ptr(), y.data_ptr(), buf.data_ptr(),
+                  _lib.stream(x.device))
     return y
 
 
@@ -93,9 +92,9 @@ def linear(x, w, bias=None, residual=None, act=None):
     nbytes = L.dm4d_linear_scratch_bytes(M, K, N)
     buf = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes > 256 and not act else None
     with torch.cuda.device(x.device):
-        _lib.check(L.dm4d_linear_f16(M, K, N, x.data_ptr(), w.data_ptr(), 0 if bias is None else bias.data_ptr(),
-                                     0 if residual is None else residual.data_ptr(), y.data_ptr(), 1 if act else 0,
-                                     0 if buf is None else buf.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream), "dm4d_linear_f16")
+        _lib.call("dm4d_linear_f16", M, K, N, x.data_ptr(), w.data_ptr(), 0 if bias is None else bias.data_ptr(),
+                  0 if residual is None else residual.data_ptr(), y.data_ptr(), 1 if act else 0, 0 if buf is None else buf.data_ptr(),
+                  _lib.stream(x.device))
     return y
 
 
@@ -185,8 +184,7 @@ class _ConvFirstFrozen(torch.autograd.Function):
         FLOPS[0] += 2 * N * H * W * Ci * C * 9
         dx = torch.empty((N, Ci, H, W), device=dy.device, dtype=torch.float16, memory_format=torch.channels_last)
         with torch.cuda.device(dy.device):
-            _lib.check(_lib.lib().dm4d_conv3x3_c128_small_nhwc_f16(N, H, W, Ci, dy.data_ptr(), w_t.data_ptr(), dx.data_ptr(),
-                                                                   torch.cuda.current_stream(dy.device).cuda_stream), "dm4d_conv3x3_c128_small_nhwc_f16")
+            _lib.call("dm4d_conv3x3_c128_small_nhwc_f16", N, H, W, Ci, dy.data_ptr(), w_t.data_ptr(), dx.data_ptr(), _lib.stream(dy.device))
         return dx, None, None, None, None, None
 
 
@@ -223,8 +221,7 @@ def conv3x3_s2_dgrad(dy, w_cls, in_shape):
     dx = torch.empty((N, Ci, H, W), device=dy.device, dtype=torch.float16, memory_format=torch.channels_last)
     ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in w_cls])
     with torch.cuda.device(dy.device):
-        _lib.check(_lib.lib().dm4d_conv3x3_s2_dgrad_nhwc_f16(N, H, W, Ci, Co, dy.data_ptr(), ptrs, dx.data_ptr(),
-                                                              torch.cuda.current_stream(dy.device).cuda_stream), "dm4d_conv3x3_s2_dgrad_nhwc_f16")
+        _lib.call("dm4d_conv3x3_s2_dgrad_nhwc_f16", N, H, W, Ci, Co, dy.data_ptr(), ptrs, dx.data_ptr(), _lib.stream(dy.device))
     return dx
 
 
@@ -277,7 +274,6 @@ def attention_qkv(qkv, scale=None):
     out = torch.empty(B, L, H * D, dtype=torch.float16, device=qkv.device)
     base, es = qkv.data_ptr(), 2
     with torch.cuda.device(qkv.device):
-        _lib.check(_lib.lib().dm4d_attention_f16(B, L, H, D, base, base + H * D * es, base + 2 * H * D * es, L * 3 * H * D, 3 * H * D,
-                                                 out.data_ptr(), float(D ** -0.5 if scale is None else scale),
-                                                 torch.cuda.current_stream(qkv.device).cuda_stream), "dm4d_attention_f16")
+        _lib.call("dm4d_attention_f16", B, L, H, D, base, base + H * D * es, base + 2 * H * D * es, L * 3 * H * D, 3 * H * D, out.data_ptr(),
+                  float(D ** -0.5 if scale is None else scale), _lib.stream(qkv.device))
     return out

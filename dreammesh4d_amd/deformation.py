@@ -146,9 +146,7 @@ class _DeformMLP(torch.autograd.Function):
         scratch = torch.empty(L.dm4d_deform_mlp_scratch_bytes(P, IN, n_heads), dtype=torch.uint8, device=dev)
         optr = (C.c_void_p * 4)(*[o.data_ptr() for o in outs])
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_deform_mlp_forward(P, f.data_ptr(), C.byref(w), h.data_ptr(), y.data_ptr(), optr,
-                                                 scratch.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                       "dm4d_deform_mlp_forward")
+            _lib.call("dm4d_deform_mlp_forward", P, f.data_ptr(), C.byref(w), h.data_ptr(), y.data_ptr(), optr, scratch.data_ptr(), _lib.stream(dev))
         ctx.w, ctx.keep, ctx.n_heads = w, (f, ps, h, y, scratch), n_heads
         ctx.set_materialize_grads(False)     # an unused head arrives as None (the C call takes NULL), not as a zero tensor
         return tuple(outs)
@@ -159,7 +157,6 @@ class _DeformMLP(torch.autograd.Function):
 
         from . import _lib
 
-        L = _lib.lib()
         f, ps, h, y, scratch = ctx.keep
         dev = f.device
         P = int(f.shape[0])
@@ -172,9 +169,8 @@ class _DeformMLP(torch.autograd.Function):
         for k in range(ctx.n_heads):
             gw.W1[k], gw.b1[k], gw.W2[k], gw.b2[k] = (grads[2 + 4 * k + j].data_ptr() for j in range(4))
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_deform_mlp_backward(P, f.data_ptr(), C.byref(ctx.w), h.data_ptr(), y.data_ptr(), gptr,
-                                                  g_feat.data_ptr(), C.byref(gw), scratch.data_ptr(),
-                                                  torch.cuda.current_stream(dev).cuda_stream), "dm4d_deform_mlp_backward")
+            _lib.call("dm4d_deform_mlp_backward", P, f.data_ptr(), C.byref(ctx.w), h.data_ptr(), y.data_ptr(), gptr, g_feat.data_ptr(), C.byref(gw),
+                      scratch.data_ptr(), _lib.stream(dev))
         return (g_feat, None, *grads)
 
 
@@ -201,7 +197,7 @@ class _NodeNetwork(torch.autograd.Function):
         B, M, S = int(timestamps.shape[0]), plan.M, plan.S
         P, IN = B * M, S * 32
         t = timestamps.detach().to(torch.float32).contiguous()
-        flags = hx.plane_layout(pl) | 4          # DM4D_HEX_CHANNELS_LAST?, DM4D_HEX_TIMES_01
+        flags = hx.plane_layout(pl) | _lib.DM4D_HEX_TIMES_01
         W0, b0 = ps[0], ps[1]
         heads = [ps[2 + 4 * k: 6 + 4 * k] for k in range(n_heads)]
         w = _lib.MlpWeights()
@@ -218,9 +214,8 @@ class _NodeNetwork(torch.autograd.Function):
         scratch = torch.empty(L.dm4d_nodenet_scratch_bytes(S, M, B, n_heads), dtype=torch.uint8, device=dev)
         optr = (C.c_void_p * 4)(*[o.data_ptr() for o in outs])
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_nodenet_forward(S, M, B, plan.res_c, hx._plane_ptr_array(pl), flags, plan.aabb_c, plan.nodes.data_ptr(),
-                                              t.data_ptr(), C.byref(w), feat.data_ptr(), samples.data_ptr(), h.data_ptr(), y.data_ptr(),
-                                              optr, scratch.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "dm4d_nodenet_forward")
+            _lib.call("dm4d_nodenet_forward", S, M, B, plan.res_c, hx._plane_ptr_array(pl), flags, plan.aabb_c, plan.nodes.data_ptr(), t.data_ptr(),
+                      C.byref(w), feat.data_ptr(), samples.data_ptr(), h.data_ptr(), y.data_ptr(), optr, scratch.data_ptr(), _lib.stream(dev))
         ctx.plan, ctx.w, ctx.flags, ctx.n_heads = plan, w, flags, n_heads
         ctx.keep = (t, pl, ps, feat, samples, h, y, scratch)
         # (in-place gradient planes only when EVERY plane is a trainable leaf: a frozen plane must not receive a `.grad` an
@@ -236,7 +231,6 @@ class _NodeNetwork(torch.autograd.Function):
 
         from . import _lib, hexplane as hx
 
-        L = _lib.lib()
         plan, n_heads = ctx.plan, ctx.n_heads
         t, pl, ps, feat, samples, h, y, scratch = ctx.keep
         dev = t.device
@@ -257,17 +251,17 @@ class _NodeNetwork(torch.autograd.Function):
                                                 for b, p in zip(plan.grad_buffers, pl)):
                 plan.grad_buffers = [torch.zeros_like(p, memory_format=torch.preserve_format) for p in pl]
             pg = plan.grad_buffers
-            flags |= 2        # DM4D_HEX_KEEP_SPATIAL
+            flags |= _lib.DM4D_HEX_KEEP_SPATIAL
         else:
             pg = [torch.empty_like(p, memory_format=torch.preserve_format) for p in pl]
         sp, tp = plan.sp, plan.tp
         _p = lambda x: x.data_ptr()
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_nodenet_backward(
+            _lib.call("dm4d_nodenet_backward",
                 S, M, B, plan.res_c, hx._plane_ptr_array(pl), flags, plan.aabb_c, _p(plan.nodes), _p(t), C.byref(ctx.w), _p(feat), _p(samples),
                 _p(h), _p(y), gptr, plan.n_sp, _p(sp["scale"]), _p(sp["plane"]), _p(sp["texel"]), _p(sp["off"]), _p(sp["item"]),
                 plan.n_tp, _p(tp["scale"]), _p(tp["plane"]), _p(tp["col"]), _p(tp["off"]), _p(tp["item"]), _p(g_feat),
-                hx._plane_ptr_array(pg), C.byref(gw), _p(scratch), torch.cuda.current_stream(dev).cuda_stream), "dm4d_nodenet_backward")
+                hx._plane_ptr_array(pg), C.byref(gw), _p(scratch), _lib.stream(dev))
         ctx.keep = None
         if in_place:
             for p, gbuf in zip(ctx.plane_params, pg):

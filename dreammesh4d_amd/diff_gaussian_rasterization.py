@@ -46,12 +46,9 @@ def _f32(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
-def _ptr(t):
+def _nonempty(t):
+    """Device pointer of `t`; NULL for None and for a tensor without elements."""
     return None if t is None or t.numel() == 0 else t.data_ptr()
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 class _Call:
@@ -85,11 +82,11 @@ class _Call:
             raise ValueError("6-channel colors_precomp needs a 6-element bg")
         self.settings = _lib.RasterSettings(self.H, self.W, float(rs.tanfovx), float(rs.tanfovy),
                                             float(rs.scale_modifier), int(rs.sh_degree), int(bool(rs.prefiltered)),
-                                            int(bool(rs.debug)), _ptr(keep["bg"]), _ptr(keep["view"]),
-                                            _ptr(keep["proj"]), _ptr(keep["campos"]))
-        self.inputs = _lib.RasterInputs(self.N, self.M, self.C, _ptr(keep["means3D"]), _ptr(keep["sh"]), _ptr(keep["col"]),
-                                        _ptr(keep["opac"]), _ptr(keep["scales"]), _ptr(keep["rots"]),
-                                        _ptr(keep["cov"]))
+                                            int(bool(rs.debug)), _nonempty(keep["bg"]), _nonempty(keep["view"]),
+                                            _nonempty(keep["proj"]), _nonempty(keep["campos"]))
+        self.inputs = _lib.RasterInputs(self.N, self.M, self.C, _nonempty(keep["means3D"]), _nonempty(keep["sh"]), _nonempty(keep["col"]),
+                                        _nonempty(keep["opac"]), _nonempty(keep["scales"]), _nonempty(keep["rots"]),
+                                        _nonempty(keep["cov"]))
 
 
 def _bytes(n, dev):
@@ -110,26 +107,24 @@ class _RasterizeGaussians(torch.autograd.Function):
         call = _Call(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
         dev, N, H, W = call.dev, call.N, call.H, call.W
         with torch.cuda.device(dev):
-            st = _stream(dev)
+            st = _lib.stream(dev)
             color = torch.empty(call.C, H, W, dtype=torch.float32, device=dev)
             depth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
             alpha = torch.empty(1, H, W, dtype=torch.float32, device=dev)
             radii = torch.empty(N, dtype=torch.int32, device=dev)
             geom_bytes = L.dm4d_raster_geom_bytes(N, H, W)
             geom = _bytes(geom_bytes, dev)
-            _lib.check(L.dm4d_rasterize_prepare(call.settings, call.inputs, _ptr(radii), geom.data_ptr(), geom_bytes,
-                                                st), "dm4d_rasterize_prepare")
+            _lib.call("dm4d_rasterize_prepare", call.settings, call.inputs, _nonempty(radii), geom.data_ptr(), geom_bytes, st)
             # the one host sync the upstream operator also has (sizing the duplicate list); the same read
             # returns the number of backward records
             import ctypes as _C
             cD, cR = _C.c_int64(0), _C.c_int64(0)
-            _lib.check(L.dm4d_rasterize_counts(geom.data_ptr(), _C.byref(cD), _C.byref(cR), st), "dm4d_rasterize_counts")
+            _lib.call("dm4d_rasterize_counts", geom.data_ptr(), _C.byref(cD), _C.byref(cR), st)
             D, R = int(cD.value), int(cR.value)
             binning = _bytes(L.dm4d_raster_binning_bytes(D), dev)
             image = _bytes(L.dm4d_raster_image_bytes(H, W), dev)
-            _lib.check(L.dm4d_rasterize_render(call.settings, call.inputs, _ptr(radii), geom.data_ptr(),
-                                               binning.data_ptr(), D, image.data_ptr(), color.data_ptr(),
-                                               depth.data_ptr(), alpha.data_ptr(), st), "dm4d_rasterize_render")
+            _lib.call("dm4d_rasterize_render", call.settings, call.inputs, _nonempty(radii), geom.data_ptr(), binning.data_ptr(), D, image.data_ptr(),
+                      color.data_ptr(), depth.data_ptr(), alpha.data_ptr(), st)
         ctx.call = call
         ctx.num_rendered = int(D)
         ctx.num_records = int(R)
@@ -150,7 +145,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         s_m3, s_m2, s_sh, s_col, s_op, s_sc, s_rot, s_cov = ctx.shapes
         f = dict(dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            st = _stream(dev)
+            st = _lib.stream(dev)
             g_color = _f32(grad_color, dev) if grad_color is not None else torch.zeros(call.C, H, W, **f)
             g_depth = _f32(grad_depth, dev) if grad_depth is not None else None
             g_alpha = _f32(grad_alpha, dev) if grad_alpha is not None else None
@@ -165,11 +160,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             d_cov = torch.empty(N, 6, **f) if not has_sr else None
             R = ctx.num_records
             grad = _bytes(L.dm4d_raster_grad_bytes(R, call.C), dev)
-            _lib.check(L.dm4d_rasterize_backward(
-                call.settings, call.inputs, _ptr(radii), geom.data_ptr(), binning.data_ptr(), D, image.data_ptr(),
-                grad.data_ptr(), R, g_color.data_ptr(), _ptr(g_depth), _ptr(g_alpha), _ptr(d_m2), _ptr(d_m3),
-                _ptr(d_op), _ptr(d_col), _ptr(d_sh), _ptr(d_sc), _ptr(d_rot), _ptr(d_cov), st),
-                "dm4d_rasterize_backward")
+            _lib.call("dm4d_rasterize_backward",
+                call.settings, call.inputs, _nonempty(radii), geom.data_ptr(), binning.data_ptr(), D, image.data_ptr(),
+                grad.data_ptr(), R, g_color.data_ptr(), _nonempty(g_depth), _nonempty(g_alpha), _nonempty(d_m2), _nonempty(d_m3),
+                _nonempty(d_op), _nonempty(d_col), _nonempty(d_sh), _nonempty(d_sc), _nonempty(d_rot), _nonempty(d_cov), st)
         # ctx.call stays (it only holds the detached inputs, the workspaces are saved tensors the C backward does not
         # modify): a second backward through the operator -- retain_graph=True, two losses -- works as upstream's does
 
@@ -187,7 +181,6 @@ class GaussianRasterizer(nn.Module):
         self.raster_settings = raster_settings
 
     def markVisible(self, positions):
-        L = _lib.lib()
         with torch.no_grad():
             rs = self.raster_settings
             dev = positions.device
@@ -195,8 +188,7 @@ class GaussianRasterizer(nn.Module):
             view = _f32(rs.viewmatrix, dev)
             present = torch.empty(pos.shape[0], dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
-                _lib.check(L.dm4d_mark_visible(pos.shape[0], _ptr(pos), _ptr(view), _ptr(present), _stream(dev)),
-                           "dm4d_mark_visible")
+                _lib.call("dm4d_mark_visible", pos.shape[0], _nonempty(pos), _nonempty(view), _nonempty(present), _lib.stream(dev))
         return present.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,

@@ -113,8 +113,7 @@ class GradAllReducer:
 
             seg = self._segments(False)
             with torch.cuda.device(flat.device):
-                _lib.check(_lib.lib().dm4d_grad_pack(C.byref(seg), flat.data_ptr(),
-                                                     torch.cuda.current_stream(flat.device).cuda_stream), "dm4d_grad_pack")
+                _lib.call("dm4d_grad_pack", C.byref(seg), flat.data_ptr(), _lib.stream(flat.device))
             return
         for p, o, ix in zip(self.params, self.offsets, self.index):
             n = p.numel() if ix is None else ix.numel()
@@ -135,8 +134,7 @@ class GradAllReducer:
 
             seg = self._segments(True)
             with torch.cuda.device(flat.device):
-                _lib.check(_lib.lib().dm4d_grad_unpack(C.byref(seg), flat.data_ptr(), float(scale),
-                                                       torch.cuda.current_stream(flat.device).cuda_stream), "dm4d_grad_unpack")
+                _lib.call("dm4d_grad_unpack", C.byref(seg), flat.data_ptr(), float(scale), _lib.stream(flat.device))
             return
         flat.mul_(scale)
         for p, o, ix in zip(self.params, self.offsets, self.index):
@@ -340,12 +338,12 @@ class ShardedAdamW:
             seg.index[k] = None if ix is None else ix.data_ptr()
             seg.count[k] = p.numel() if ix is None else ix.numel()
             seg.offset[k] = o
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st = _lib.stream(dev)
         with torch.cuda.device(dev):
             if fn == "dm4d_grad_pack":
-                _lib.check(_lib.lib().dm4d_grad_pack(C.byref(seg), self.padded.data_ptr(), st), fn)
+                _lib.call("dm4d_grad_pack", C.byref(seg), self.padded.data_ptr(), st)
             else:
-                _lib.check(_lib.lib().dm4d_grad_unpack(C.byref(seg), self.padded.data_ptr(), 1.0, st), fn)
+                _lib.call("dm4d_grad_unpack", C.byref(seg), self.padded.data_ptr(), 1.0, st)
 
     @torch.no_grad()
     def step(self, found_inf=None):
@@ -394,7 +392,7 @@ class ShardedAdamW:
             # pack -> reduce-scatter -> the kernel on this rank's slice -> all-gather -> unpack into the parameters
             seg0 = red._segments(False)
             with torch.cuda.device(dev):
-                _lib.check(_lib.lib().dm4d_grad_pack(C.byref(seg0), self.padded.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "dm4d_grad_pack")
+                _lib.call("dm4d_grad_pack", C.byref(seg0), self.padded.data_ptr(), _lib.stream(dev))
             g_slice = self._g_slice
             if dist.get_backend() == "gloo":
                 # (functional rehearsal on a shared device: the SAME all-reduce over the SAME n elements as the replicated path, then this
@@ -426,7 +424,7 @@ class ShardedAdamW:
             scale = 1.0 / w
             # (a step skipped by found_inf still fills the send slice: the kernel copies the CURRENT parameter values into param_out)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().dm4d_adamw_step(C.byref(seg), C.byref(a), scale, torch.cuda.current_stream(dev).cuda_stream), "dm4d_adamw_step")
+            _lib.call("dm4d_adamw_step", C.byref(seg), C.byref(a), scale, _lib.stream(dev))
         if w > 1:
             if dist.get_backend() == "gloo":
                 parts = [torch.empty(self.chunk, dtype=torch.float32) for _ in range(w)]

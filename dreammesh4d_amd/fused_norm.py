@@ -16,8 +16,8 @@ import torch.nn.functional as F
 
 from . import _lib
 
-_DTYPES = {torch.float16: 0, torch.float32: 1}      # DM4D_GN_F16, DM4D_GN_F32
-MAX_SPLITS = 128                                    # DM4D_GN_MAX_SPLITS
+_DTYPES = {torch.float16: _lib.DM4D_GN_F16, torch.float32: _lib.DM4D_GN_F32}
+MAX_SPLITS = _lib.DM4D_GN_MAX_SPLITS
 
 # A tensor on a HIP device that does NOT take the HIP operator (a layout regression upstream: NCHW activations, an odd
 # channel count, a dtype mismatch) silently costs the step its fused kernels.  Every such call is counted here, by operator
@@ -75,17 +75,15 @@ class _GroupNormNHWC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, add, groups, eps, silu, skip=False):
         N, C, H, W = x.shape
-        L = _lib.lib()
         y = torch.empty_like(x)                                    # same (channels-last) strides
         S = _splits(H * W)
         stats = torch.empty(N, groups, 2, device=x.device, dtype=torch.float32)
         scratch = torch.empty(N, S, groups, 2, device=x.device, dtype=torch.float32)
         add_stride = 0 if add is None or add.dim() == 1 else int(add.stride(0))     # [C]: the same for every sample; [N, C]: rows may be strided
         with torch.cuda.device(x.device):
-            _lib.check(L.dm4d_groupnorm_nhwc_forward(N, H * W, C, groups, _DTYPES[x.dtype], x.data_ptr(),
-                                                 0 if add is None else add.data_ptr(), add_stride, weight.data_ptr(), bias.data_ptr(),
-                                                 eps, int(silu), y.data_ptr(), stats.data_ptr(), scratch.data_ptr(), S,
-                                                 torch.cuda.current_stream(x.device).cuda_stream), "groupnorm forward")
+            _lib.call("dm4d_groupnorm_nhwc_forward", N, H * W, C, groups, _DTYPES[x.dtype], x.data_ptr(), 0 if add is None else add.data_ptr(),
+                      add_stride, weight.data_ptr(), bias.data_ptr(), eps, int(silu), y.data_ptr(), stats.data_ptr(), scratch.data_ptr(), S,
+                      _lib.stream(x.device))
         ctx.save_for_backward(x, weight, bias, stats, add)
         ctx.cfg = (groups, bool(silu), S, add_stride)
         if skip:
@@ -106,15 +104,12 @@ class _GroupNormNHWC(torch.autograd.Function):
             dy = dy.contiguous(memory_format=torch.channels_last)
         if d_skip is not None and not (is_channels_last(d_skip) and d_skip.dtype == x.dtype):
             d_skip = d_skip.to(x.dtype).contiguous(memory_format=torch.channels_last)
-        L = _lib.lib()
         dx = torch.empty_like(x)
         scratch = torch.empty(N, S, groups, 2, device=x.device, dtype=torch.float32)
         with torch.cuda.device(x.device):
-            _lib.check(L.dm4d_groupnorm_nhwc_backward_add(N, H * W, C, groups, _DTYPES[x.dtype], x.data_ptr(),
-                                                      0 if add is None else add.data_ptr(), add_stride, weight.data_ptr(), bias.data_ptr(),
-                                                      stats.data_ptr(), int(silu), dy.data_ptr(), 0 if d_skip is None else d_skip.data_ptr(),
-                                                      dx.data_ptr(), scratch.data_ptr(), S,
-                                                      torch.cuda.current_stream(x.device).cuda_stream), "groupnorm backward")
+            _lib.call("dm4d_groupnorm_nhwc_backward_add", N, H * W, C, groups, _DTYPES[x.dtype], x.data_ptr(), 0 if add is None else add.data_ptr(),
+                      add_stride, weight.data_ptr(), bias.data_ptr(), stats.data_ptr(), int(silu), dy.data_ptr(),
+                      0 if d_skip is None else d_skip.data_ptr(), dx.data_ptr(), scratch.data_ptr(), S, _lib.stream(x.device))
         return dx, None, None, None, None, None, None, None
 
 
@@ -171,8 +166,8 @@ class _AddBias(torch.autograd.Function):
         N, C, H, W = a.shape
         y = torch.empty_like(a)
         with torch.cuda.device(a.device):
-            _lib.check(_lib.lib().dm4d_add_bias_nhwc(N * H * W, C, _DTYPES[a.dtype], a.data_ptr(), b.data_ptr(), bias.data_ptr(), y.data_ptr(),
-                                                 torch.cuda.current_stream(a.device).cuda_stream), "add_bias")
+            _lib.call("dm4d_add_bias_nhwc", N * H * W, C, _DTYPES[a.dtype], a.data_ptr(), b.data_ptr(), bias.data_ptr(), y.data_ptr(),
+                      _lib.stream(a.device))
         return y
 
     @staticmethod
@@ -197,8 +192,7 @@ def geglu(proj):
             and proj.numel() > 0 and not (torch.is_grad_enabled() and proj.requires_grad)):
         y = torch.empty(proj.shape[:-1] + (D,), device=proj.device, dtype=proj.dtype)
         with torch.cuda.device(proj.device):
-            _lib.check(_lib.lib().dm4d_geglu(proj.numel() // (2 * D), D, _DTYPES[proj.dtype], proj.data_ptr(), y.data_ptr(),
-                                         torch.cuda.current_stream(proj.device).cuda_stream), "geglu")
+            _lib.call("dm4d_geglu", proj.numel() // (2 * D), D, _DTYPES[proj.dtype], proj.data_ptr(), y.data_ptr(), _lib.stream(proj.device))
         return y
     _fallback("geglu", proj, "layout" if not proj.is_contiguous() else "dtype/width/requires_grad")
     x, gate = proj.chunk(2, dim=-1)
@@ -221,8 +215,7 @@ def add_layer_norm(norm, x, tok=None, bias2=None, want_sum=True):
     n = torch.empty_like(x)
     xb = torch.empty_like(x) if want_sum else None
     with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().dm4d_add_layernorm_f16(B * Lq, C, Lq, x.data_ptr(), 0 if tok is None else tok.data_ptr(), norm.weight.data_ptr(),
-                                                     norm.bias.data_ptr(), float(norm.eps), 0 if bias2 is None else bias2.data_ptr(), n.data_ptr(),
-                                                     0 if xb is None else xb.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream),
-                   "add_layernorm")
+        _lib.call("dm4d_add_layernorm_f16", B * Lq, C, Lq, x.data_ptr(), 0 if tok is None else tok.data_ptr(), norm.weight.data_ptr(),
+                  norm.bias.data_ptr(), float(norm.eps), 0 if bias2 is None else bias2.data_ptr(), n.data_ptr(), 0 if xb is None else xb.data_ptr(),
+                  _lib.stream(x.device))
     return n, xb

@@ -85,7 +85,6 @@ class _PointsRgbSH(torch.autograd.Function):
     def forward(ctx, sh, points, campos, degree):
         from . import _lib
 
-        L = _lib.lib()
         dev = points.device
         if dev.type != "cuda":
             raise RuntimeError("points_rgb_sh: tensors must live on a HIP device; there is no CPU path")
@@ -95,8 +94,8 @@ class _PointsRgbSH(torch.autograd.Function):
         rgb = torch.empty(N, 3, dtype=torch.float32, device=dev)
         clamped = torch.empty(N, 3, dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_sh_eval_forward(N, int(degree), M, points.data_ptr(), campos.data_ptr(), sh.data_ptr(), rgb.data_ptr(),
-                                              clamped.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "dm4d_sh_eval_forward")
+            _lib.call("dm4d_sh_eval_forward", N, int(degree), M, points.data_ptr(), campos.data_ptr(), sh.data_ptr(), rgb.data_ptr(),
+                      clamped.data_ptr(), _lib.stream(dev))
         ctx.save_for_backward(sh, points, campos, clamped)
         ctx.degree = int(degree)
         return rgb
@@ -105,16 +104,14 @@ class _PointsRgbSH(torch.autograd.Function):
     def backward(ctx, g_rgb):
         from . import _lib
 
-        L = _lib.lib()
         sh, points, campos, clamped = ctx.saved_tensors
         dev = points.device
         N, M = int(sh.shape[0]), int(sh.shape[1])
         g_rgb = g_rgb.detach().to(torch.float32).contiguous()
         d_sh, d_pts = torch.empty_like(sh), torch.empty_like(points)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_sh_eval_backward(N, ctx.degree, M, points.data_ptr(), campos.data_ptr(), sh.data_ptr(), clamped.data_ptr(),
-                                               g_rgb.data_ptr(), d_sh.data_ptr(), d_pts.data_ptr(),
-                                               torch.cuda.current_stream(dev).cuda_stream), "dm4d_sh_eval_backward")
+            _lib.call("dm4d_sh_eval_backward", N, ctx.degree, M, points.data_ptr(), campos.data_ptr(), sh.data_ptr(), clamped.data_ptr(),
+                      g_rgb.data_ptr(), d_sh.data_ptr(), d_pts.data_ptr(), _lib.stream(dev))
         return d_sh, d_pts, None, None
 
 

@@ -91,9 +91,8 @@ def _cg(L_, mat, B, x0, max_iter, tol, check_every, what):
     scratch = torch.empty(L_.dm4d_cg_batched_scratch_bytes(V, S), dtype=torch.uint8, device=dev)
     rel = C.c_double(0.0)
     with torch.cuda.device(dev):
-        it = _lib.check(L_.dm4d_cg_batched_f64(V, S, off.data_ptr(), col.data_ptr(), val.data_ptr(), dinv.data_ptr(), B.data_ptr(),
-                                               x0.data_ptr(), scratch.data_ptr(), max_iter, tol, check_every, C.byref(rel),
-                                               torch.cuda.current_stream(dev).cuda_stream), "dm4d_cg_batched_f64")
+        it = _lib.call("dm4d_cg_batched_f64", V, S, off.data_ptr(), col.data_ptr(), val.data_ptr(), dinv.data_ptr(), B.data_ptr(), x0.data_ptr(),
+                       scratch.data_ptr(), max_iter, tol, check_every, C.byref(rel), _lib.stream(dev))
     if not rel.value <= tol:
         raise _lib.Dm4dError(f"heat method: the {what} systems did not converge ({it} iterations, worst |r|/|b| = {rel.value:.2e})")
     return x0, it
@@ -277,12 +276,11 @@ def heat_geodesic_knn(verts, faces, node_xyz, K, device="cuda:0", chunk=2048, to
             _mark("heat_cg")
         XT = torch.empty(3 * F_, S, **f64)
         with torch.cuda.device(dev):
-            _lib.check(L_.dm4d_heat_face_directions(F_, S, faces_t.data_ptr(), Gt.data_ptr(), U.data_ptr(), XT.data_ptr(),
-                                                    torch.cuda.current_stream(dev).cuda_stream), "dm4d_heat_face_directions")
+            _lib.call("dm4d_heat_face_directions", F_, S, faces_t.data_ptr(), Gt.data_ptr(), U.data_ptr(), XT.data_ptr(), _lib.stream(dev))
         score = torch.matmul(Wt, XT)                                                      # [M, S] float64 GEMM (rocBLAS)
         with torch.cuda.device(dev):
-            _lib.check(L_.dm4d_graph_select_knn(S, M, K, score.data_ptr(), S, s0, vt.data_ptr(), nt.data_ptr(), idx.data_ptr(),
-                                                w.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "dm4d_graph_select_knn")
+            _lib.call("dm4d_graph_select_knn", S, M, K, score.data_ptr(), S, s0, vt.data_ptr(), nt.data_ptr(), idx.data_ptr(), w.data_ptr(),
+                      _lib.stream(dev))
         del U, XT, score
         _mark("gemm_select")
     if stats is not None:
@@ -320,8 +318,6 @@ def build_deformation_graph(verts, faces, node_xyz, nodes_connectivity=6, mode="
     idx = torch.empty(V, K, dtype=torch.int64, device=dev)
     w = torch.empty(V, K, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(L.dm4d_graph_geodesic_knn(V, M, K, off_t.data_ptr(), nbr_t.data_ptr(), len_t.data_ptr(), vt.data_ptr(),
-                                             nt.data_ptr(), node_vertex.data_ptr(), scratch.data_ptr(), idx.data_ptr(),
-                                             w.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                   "dm4d_graph_geodesic_knn")
+        _lib.call("dm4d_graph_geodesic_knn", V, M, K, off_t.data_ptr(), nbr_t.data_ptr(), len_t.data_ptr(), vt.data_ptr(), nt.data_ptr(),
+                  node_vertex.data_ptr(), scratch.data_ptr(), idx.data_ptr(), w.data_ptr(), _lib.stream(dev))
     return idx, w

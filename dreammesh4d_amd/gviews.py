@@ -14,7 +14,9 @@ import torch
 
 from . import _lib
 from .geometry import reject_sh_coefficients
-from .views import ViewRenderer, _f32, _p
+from ._lib import ptr as _p
+from .ops import _f32
+from .views import ViewRenderer
 
 
 class GaussianViews(ViewRenderer):
@@ -65,7 +67,6 @@ class GaussianViews(ViewRenderer):
 class _RenderGaussianViews(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r, means3D, rotations, scales, opacities, colors, viewmats, projmats, bg6, means2D):
-        L = _lib.lib()
         dev, N, H, W = r.device, r.N, r.H, r.W
         B = int(viewmats.shape[0])
         f = dict(dtype=torch.float32, device=dev)
@@ -77,12 +78,13 @@ class _RenderGaussianViews(torch.autograd.Function):
         out = dict(radii=torch.empty(B, N, dtype=torch.int32, device=dev), color=torch.empty(B, 6, H, W, **f),
                    depth=torch.empty(B, 1, H, W, **f), alpha=torch.empty(B, 1, H, W, **f))
         ws = r._take_ws(B)
-        vs = _lib.GViewsStruct(B, N, H, W, r.tanfov, r.tanfov, r.scale_modifier, 0 if r.deterministic else 1, r.capacity, r.record_capacity,
+        vs = _lib.GViewsStruct(B, N, H, W, r.tanfov, r.tanfov, r.scale_modifier,
+                               _lib.DM4D_RECORDS_CELL if r.deterministic else _lib.DM4D_RECORDS_TILE, r.capacity, r.record_capacity,
                                _p(keep["bg"]), _p(keep["vm"]), _p(keep["pm"]), _p(keep["m"]), _p(keep["q"]), _p(keep["s"]), _p(keep["o"]),
                                _p(keep["c"]), _p(out["radii"]), _p(out["color"]), _p(out["depth"]), _p(out["alpha"]), _p(ws["geom"]),
                                _p(ws["binning"]), _p(ws["image"]))
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_gviews_forward(C.byref(vs), torch.cuda.current_stream(dev).cuda_stream), "dm4d_gviews_forward")
+            _lib.call("dm4d_gviews_forward", C.byref(vs), _lib.stream(dev))
         ctx.save_for_backward(out["color"], out["depth"], out["alpha"], out["radii"])      # (returned tensors: not as ctx attributes, views.py)
         ctx.r, ctx.vs, ctx.keep, ctx.ws = r, vs, keep, ws
         ctx.shapes = (means3D.shape, rotations.shape, scales.shape, opacities.shape, colors.shape)
@@ -93,7 +95,6 @@ class _RenderGaussianViews(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_color, g_depth, g_alpha, _g_radii):
-        L = _lib.lib()
         r, vs = ctx.r, ctx.vs
         if ctx.ws is None:
             raise RuntimeError("render_gaussian_views: backward called a second time: the workspaces of this forward were recycled")
@@ -107,7 +108,7 @@ class _RenderGaussianViews(torch.autograd.Function):
         scr = r._bwd_scratch(B, vs.record_capacity)
         gs = _lib.GViewsGrads(_p(gc), _p(gd), _p(ga), _p(scr["grad"]), _p(o["m2"]), _p(o["m3"]), _p(o["rot"]), _p(o["sc"]), _p(o["op"]), _p(o["col"]))
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_gviews_backward(C.byref(vs), C.byref(gs), torch.cuda.current_stream(dev).cuda_stream), "dm4d_gviews_backward")
+            _lib.call("dm4d_gviews_backward", C.byref(vs), C.byref(gs), _lib.stream(dev))
         r._give_ws(ctx.ws)
         ctx.ws = None
         r.last_grads = o

@@ -10,21 +10,17 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 
 PLANE_AXES = [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]
 SPATIAL = (0, 1, 3)
 TIME = (2, 4, 5)
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 class HexPlan:
     """Static gather lists of the backward for one node set (the nodes never move)."""
 
     def __init__(self, field, nodes):
-        L = _lib.lib()
         dev = nodes.device
         self.S = len(field.grids)
         self.M = int(nodes.shape[0])
@@ -40,8 +36,7 @@ class HexPlan:
         self.nodes = nodes.detach().to(torch.float32).contiguous()
         i0 = torch.empty(self.S, 3, self.M, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_hexplane_axis_index(self.S, self.M, self.res_c, self.aabb_c, _p(self.nodes), _p(i0),
-                                                  torch.cuda.current_stream(dev).cuda_stream), "dm4d_hexplane_axis_index")
+            _lib.call("dm4d_hexplane_axis_index", self.S, self.M, self.res_c, self.aabb_c, _p(self.nodes), _p(i0), _lib.stream(dev))
         i0 = i0.cpu().numpy().astype(np.int64)
         sp = dict(scale=[], plane=[], texel=[], off=[0], item=[])
         tp = dict(scale=[], plane=[], col=[], off=[0], item=[])
@@ -87,10 +82,10 @@ class HexPlan:
 
 
 def plane_layout(planes):
-    """0 if every plane is a contiguous [1,32,H,W] tensor, 1 if every plane is in torch.channels_last memory format
+    """0 if every plane is a contiguous [1,32,H,W] tensor, DM4D_HEX_CHANNELS_LAST if every plane is in torch.channels_last memory format
     (storage [H][W][32], what `HexPlaneField` allocates: one 128-byte line per texel); anything else is an error."""
     if all(p.dtype == torch.float32 and p.is_contiguous(memory_format=torch.channels_last) and p.shape[1] > 1 for p in planes):
-        return 1
+        return _lib.DM4D_HEX_CHANNELS_LAST
     if all(p.dtype == torch.float32 and p.is_contiguous() for p in planes):
         return 0
     raise ValueError("HexPlane planes must be float32 and all contiguous or all channels_last")
@@ -114,9 +109,8 @@ class _HexPlaneFeatures(torch.autograd.Function):
         need_bwd = any(p.requires_grad for p in planes)
         samples = torch.empty(L.dm4d_hexplane_scratch_bytes(plan.S, plan.M, B), dtype=torch.uint8, device=dev) if need_bwd else None
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_hexplane_forward(plan.S, plan.M, B, plan.res_c, _plane_ptr_array(pl), cl, plan.aabb_c,
-                                               _p(plan.nodes), _p(t), _p(feat), _p(samples),
-                                               torch.cuda.current_stream(dev).cuda_stream), "dm4d_hexplane_forward")
+            _lib.call("dm4d_hexplane_forward", plan.S, plan.M, B, plan.res_c, _plane_ptr_array(pl), cl, plan.aabb_c, _p(plan.nodes), _p(t), _p(feat),
+                      _p(samples), _lib.stream(dev))
         ctx.plan, ctx.t, ctx.planes, ctx.samples, ctx.cl = plan, t, pl, samples, cl
         # grads_in_place: the Parameters themselves (leaves, not outputs: no reference cycle), see backward()
         # (only when EVERY plane is a trainable leaf: a frozen plane must never receive a `.grad`; the persistent buffers are
@@ -126,7 +120,6 @@ class _HexPlaneFeatures(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_feat):
-        L = _lib.lib()
         plan, t, pl = ctx.plan, ctx.t, ctx.planes
         dev = t.device
         B = int(t.shape[0])
@@ -145,7 +138,7 @@ class _HexPlaneFeatures(torch.autograd.Function):
                                                 for b, p in zip(plan.grad_buffers, pl)):
                 plan.grad_buffers = [torch.zeros_like(p, memory_format=torch.preserve_format) for p in pl]
             grads = plan.grad_buffers
-            flags |= 2        # DM4D_HEX_KEEP_SPATIAL
+            flags |= _lib.DM4D_HEX_KEEP_SPATIAL
         else:
             # dense, in the planes' own memory format; the C call zero-fills them (one launch) before the gathers
             grads = [torch.empty_like(p, memory_format=torch.preserve_format) for p in pl]
@@ -153,11 +146,11 @@ class _HexPlaneFeatures(torch.autograd.Function):
         scratch, ctx.samples = ctx.samples, None      # the forward's plane samples; the backward works in place
         sp, tp = plan.sp, plan.tp
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_hexplane_backward(
+            _lib.call("dm4d_hexplane_backward",
                 plan.S, plan.M, B, plan.res_c, _plane_ptr_array(pl), flags, plan.aabb_c, _p(plan.nodes), _p(t), _p(g),
                 plan.n_sp, _p(sp["scale"]), _p(sp["plane"]), _p(sp["texel"]), _p(sp["off"]), _p(sp["item"]),
                 plan.n_tp, _p(tp["scale"]), _p(tp["plane"]), _p(tp["col"]), _p(tp["off"]), _p(tp["item"]),
-                _p(scratch), gptr, torch.cuda.current_stream(dev).cuda_stream), "dm4d_hexplane_backward")
+                _p(scratch), gptr, _lib.stream(dev))
         if in_place:
             for p, gbuf in zip(ctx.params, grads):
                 p.grad = gbuf

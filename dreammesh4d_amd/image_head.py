@@ -21,10 +21,9 @@ class _ImageHead(torch.autograd.Function):
         partial = torch.empty(B, nb, 2, dtype=torch.float32, device=dev)
         half = torch.empty(n_rnd, H // 2, W // 2, 3, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_image_head_forward(B, H, W, C, c.data_ptr(), a.data_ptr(), ref_pos.data_ptr(), rnd_pos.data_ptr(),
-                                                 ref_images.data_ptr(), ref_masks.data_ptr(), fidx_ref.data_ptr(), n_ref, n_rnd,
-                                                 partial.data_ptr(), half.data_ptr() if n_rnd else 0,
-                                                 torch.cuda.current_stream(dev).cuda_stream), "dm4d_image_head_forward")
+            _lib.call("dm4d_image_head_forward", B, H, W, C, c.data_ptr(), a.data_ptr(), ref_pos.data_ptr(), rnd_pos.data_ptr(),
+                      ref_images.data_ptr(), ref_masks.data_ptr(), fidx_ref.data_ptr(), n_ref, n_rnd, partial.data_ptr(),
+                      half.data_ptr() if n_rnd else 0, _lib.stream(dev))
         ctx.save_for_backward(c, a, ref_pos, rnd_pos, ref_images, ref_masks, fidx_ref)
         ctx.n = (n_ref, n_rnd)
         from .loss_sum import partial_sums
@@ -35,7 +34,6 @@ class _ImageHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_rgb, g_mask, g_half):
-        L = _lib.lib()
         c, a, ref_pos, rnd_pos, ref_images, ref_masks, fidx_ref = ctx.saved_tensors
         n_ref, n_rnd = ctx.n
         B, C, H, W = c.shape
@@ -45,10 +43,9 @@ class _ImageHead(torch.autograd.Function):
         g_rgb, g_mask, g_half = f(g_rgb), f(g_mask), f(g_half)
         p = lambda t: 0 if t is None else t.data_ptr()
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_image_head_backward(B, H, W, C, c.data_ptr(), a.data_ptr(), ref_pos.data_ptr(), rnd_pos.data_ptr(),
-                                                  ref_images.data_ptr(), ref_masks.data_ptr(), fidx_ref.data_ptr(), n_ref, n_rnd,
-                                                  p(g_rgb), p(g_mask), p(g_half) if n_rnd else 0, gc.data_ptr(), ga.data_ptr(),
-                                                  torch.cuda.current_stream(dev).cuda_stream), "dm4d_image_head_backward")
+            _lib.call("dm4d_image_head_backward", B, H, W, C, c.data_ptr(), a.data_ptr(), ref_pos.data_ptr(), rnd_pos.data_ptr(),
+                      ref_images.data_ptr(), ref_masks.data_ptr(), fidx_ref.data_ptr(), n_ref, n_rnd, p(g_rgb), p(g_mask), p(g_half) if n_rnd else 0,
+                      gc.data_ptr(), ga.data_ptr(), _lib.stream(dev))
         return gc, ga, None, None, None, None, None, None, None
 
 

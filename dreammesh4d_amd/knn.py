@@ -25,12 +25,11 @@ def _knn_one(L, q, p, K, exclude, method, dists, idx32):
     dev = q.device
     nq, np_ = int(q.shape[0]), int(p.shape[0])
     with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st = _lib.stream(dev)
         nbytes = int(L.dm4d_knn_points_scratch_bytes(nq, np_, K, method))
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-        _lib.check(L.dm4d_knn_points(nq, np_, K, q.data_ptr(), p.data_ptr(), 1 if exclude else 0, method,
-                                     None if scratch is None else scratch.data_ptr(), nbytes, dists.data_ptr(), idx32.data_ptr(), st),
-                   "dm4d_knn_points")
+        _lib.call("dm4d_knn_points", nq, np_, K, q.data_ptr(), p.data_ptr(), 1 if exclude else 0, method,
+                  None if scratch is None else scratch.data_ptr(), nbytes, dists.data_ptr(), idx32.data_ptr(), st)
 
 
 def knn_points(p1, p2, K, exclude_self=False, method="auto"):

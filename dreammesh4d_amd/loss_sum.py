@@ -22,8 +22,7 @@ def partial_sums(partial, matrix):
     out = torch.empty(m, dtype=torch.float32, device=partial.device)
     flat = (C.c_float * (k * m))(*[float(v) for row in matrix for v in row])
     with torch.cuda.device(partial.device):
-        _lib.check(_lib.lib().dm4d_partial_sums(n, k, m, partial.data_ptr(), flat, out.data_ptr(),
-                                                torch.cuda.current_stream(partial.device).cuda_stream), "dm4d_partial_sums")
+        _lib.call("dm4d_partial_sums", n, k, m, partial.data_ptr(), flat, out.data_ptr(), _lib.stream(partial.device))
     return out
 
 
@@ -48,7 +47,7 @@ class _WeightedSum(torch.autograd.Function):
         ctx.w, ctx.n, ctx.seg = (C.c_float * n)(*w), n, seg
         out = torch.empty((), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().dm4d_weighted_sum(n, cp, ctx.w, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "dm4d_weighted_sum")
+            _lib.call("dm4d_weighted_sum", n, cp, ctx.w, out.data_ptr(), _lib.stream(dev))
         return out
 
     @staticmethod
@@ -56,8 +55,7 @@ class _WeightedSum(torch.autograd.Function):
         g = g.detach().to(torch.float32).contiguous()
         out = torch.empty(ctx.n, dtype=torch.float32, device=g.device)
         with torch.cuda.device(g.device):
-            _lib.check(_lib.lib().dm4d_weighted_sum_backward(ctx.n, g.data_ptr(), ctx.w, out.data_ptr(),
-                                                             torch.cuda.current_stream(g.device).cuda_stream), "dm4d_weighted_sum_backward")
+            _lib.call("dm4d_weighted_sum_backward", ctx.n, g.data_ptr(), ctx.w, out.data_ptr(), _lib.stream(g.device))
         return (None,) + tuple(out[a] if k is None else out[a:a + k] for a, k in ctx.seg)      # (views: no launches)
 
 

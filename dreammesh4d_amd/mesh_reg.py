@@ -57,24 +57,20 @@ def _cot_weight_matrix(verts, faces):
 class _ArapEnergy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, coach, xyz, rot):
-        L = _lib.lib()
         dev = coach.device
         x = xyz.detach().to(torch.float32).contiguous()
         r = rot.detach().to(torch.float32).contiguous()
         T, V = int(x.shape[0]), coach.n_verts
         ev = torch.empty(T, V, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_arap_energy_forward(T, V, coach._off.data_ptr(), coach._nbr.data_ptr(), coach._rev.data_ptr(),
-                                                  coach._w.data_ptr(), coach._e.data_ptr(), x.data_ptr(), r.data_ptr(),
-                                                  ev.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                       "dm4d_arap_energy_forward")
+            _lib.call("dm4d_arap_energy_forward", T, V, coach._off.data_ptr(), coach._nbr.data_ptr(), coach._rev.data_ptr(), coach._w.data_ptr(),
+                      coach._e.data_ptr(), x.data_ptr(), r.data_ptr(), ev.data_ptr(), _lib.stream(dev))
         ctx.coach = coach
         ctx.save_for_backward(x, r)
         return ev.sum(dim=1)
 
     @staticmethod
     def backward(ctx, g_energy):
-        L = _lib.lib()
         coach = ctx.coach
         x, r = ctx.saved_tensors
         dev = coach.device
@@ -83,26 +79,21 @@ class _ArapEnergy(torch.autograd.Function):
         gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
         gr = torch.empty_like(r) if ctx.needs_input_grad[2] else None
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_arap_energy_backward(T, V, coach._off.data_ptr(), coach._nbr.data_ptr(), coach._rev.data_ptr(),
-                                                   coach._w.data_ptr(), coach._e.data_ptr(), x.data_ptr(), r.data_ptr(),
-                                                   g.data_ptr(), None if gx is None else gx.data_ptr(),
-                                                   None if gr is None else gr.data_ptr(),
-                                                   torch.cuda.current_stream(dev).cuda_stream), "dm4d_arap_energy_backward")
+            _lib.call("dm4d_arap_energy_backward", T, V, coach._off.data_ptr(), coach._nbr.data_ptr(), coach._rev.data_ptr(), coach._w.data_ptr(),
+                      coach._e.data_ptr(), x.data_ptr(), r.data_ptr(), g.data_ptr(), None if gx is None else gx.data_ptr(),
+                      None if gr is None else gr.data_ptr(), _lib.stream(dev))
         return None, gx, gr
 
 
 def _fit_rotations(coach, x, want_flags=False):
     """x [T,V,3] float32 contiguous on the coach's device -> R [T,V,3,3] (and the flag bytes [T,V])."""
-    L = _lib.lib()
     dev = coach.device
     T, V = int(x.shape[0]), coach.n_verts
     R = torch.empty(T, V, 3, 3, dtype=torch.float32, device=dev)
     flags = torch.empty(T, V, dtype=torch.uint8, device=dev) if want_flags else None
     with torch.cuda.device(dev):
-        _lib.check(L.dm4d_arap_fit_rotations(T, V, coach._off.data_ptr(), coach._nbr.data_ptr(), coach._w.data_ptr(),
-                                             coach._e.data_ptr(), x.data_ptr(), R.data_ptr(),
-                                             None if flags is None else flags.data_ptr(),
-                                             torch.cuda.current_stream(dev).cuda_stream), "dm4d_arap_fit_rotations")
+        _lib.call("dm4d_arap_fit_rotations", T, V, coach._off.data_ptr(), coach._nbr.data_ptr(), coach._w.data_ptr(), coach._e.data_ptr(),
+                  x.data_ptr(), R.data_ptr(), None if flags is None else flags.data_ptr(), _lib.stream(dev))
     return R, flags
 
 
@@ -216,22 +207,19 @@ class ARAPCoach:
 class _NormalConsistency(torch.autograd.Function):
     @staticmethod
     def forward(ctx, nc, xyz):
-        L = _lib.lib()
         dev = nc.device
         x = xyz.detach().to(torch.float32).contiguous()
         T = int(x.shape[0])
         terms = torch.empty(T, nc.n_pairs, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_normal_consistency_forward(T, nc.n_verts, nc.n_pairs, nc._pairs.data_ptr(), x.data_ptr(),
-                                                         terms.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                       "dm4d_normal_consistency_forward")
+            _lib.call("dm4d_normal_consistency_forward", T, nc.n_verts, nc.n_pairs, nc._pairs.data_ptr(), x.data_ptr(), terms.data_ptr(),
+                      _lib.stream(dev))
         ctx.nc = nc
         ctx.save_for_backward(x)
         return terms.sum(dim=1) / float(max(nc.n_pairs, 1))
 
     @staticmethod
     def backward(ctx, g_loss):
-        L = _lib.lib()
         nc = ctx.nc
         (x,) = ctx.saved_tensors
         dev = nc.device
@@ -240,10 +228,8 @@ class _NormalConsistency(torch.autograd.Function):
         gx = torch.empty_like(x)
         roles = torch.empty(T, max(nc.n_pairs, 1), 12, dtype=torch.float32, device=dev)      # the pairs' per-vertex gradient vectors
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_normal_consistency_backward_scratch(T, nc.n_verts, nc.n_pairs, nc._pairs.data_ptr(), nc._off.data_ptr(),
-                                                          nc._items.data_ptr(), x.data_ptr(), g.data_ptr(), gx.data_ptr(),
-                                                          roles.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                       "dm4d_normal_consistency_backward_scratch")
+            _lib.call("dm4d_normal_consistency_backward_scratch", T, nc.n_verts, nc.n_pairs, nc._pairs.data_ptr(), nc._off.data_ptr(),
+                      nc._items.data_ptr(), x.data_ptr(), g.data_ptr(), gx.data_ptr(), roles.data_ptr(), _lib.stream(dev))
         return None, gx
 
 
@@ -296,23 +282,20 @@ class MeshNormalConsistency:
 class _LaplacianSmoothing(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ls, xyz):
-        L = _lib.lib()
         dev = ls.device
         x = xyz.detach().to(torch.float32).contiguous()
         T = int(x.shape[0])
         terms = torch.empty(T, ls.n_verts, dtype=torch.float32, device=dev)
         unit = torch.empty(T, ls.n_verts, 3, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_laplacian_smoothing_forward(T, ls.n_verts, ls._off.data_ptr(), ls._nbr.data_ptr(), x.data_ptr(),
-                                                          terms.data_ptr(), unit.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                       "dm4d_laplacian_smoothing_forward")
+            _lib.call("dm4d_laplacian_smoothing_forward", T, ls.n_verts, ls._off.data_ptr(), ls._nbr.data_ptr(), x.data_ptr(), terms.data_ptr(),
+                      unit.data_ptr(), _lib.stream(dev))
         ctx.ls = ls
         ctx.save_for_backward(unit)
         return terms.sum(dim=1) / float(max(ls.n_verts, 1))
 
     @staticmethod
     def backward(ctx, g_loss):
-        L = _lib.lib()
         ls = ctx.ls
         (unit,) = ctx.saved_tensors
         dev = ls.device
@@ -320,9 +303,8 @@ class _LaplacianSmoothing(torch.autograd.Function):
         g = g_loss.detach().to(torch.float32).contiguous()
         gx = torch.empty_like(unit)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_laplacian_smoothing_backward(T, ls.n_verts, ls._off.data_ptr(), ls._nbr.data_ptr(), unit.data_ptr(),
-                                                           g.data_ptr(), gx.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                       "dm4d_laplacian_smoothing_backward")
+            _lib.call("dm4d_laplacian_smoothing_backward", T, ls.n_verts, ls._off.data_ptr(), ls._nbr.data_ptr(), unit.data_ptr(), g.data_ptr(),
+                      gx.data_ptr(), _lib.stream(dev))
         return None, gx
 
 

@@ -86,13 +86,12 @@ def simplify_vertex_clustering(verts, faces, colors=None, scale=64, voxel_size=N
     if dev.type != "cuda" or faces.device != dev or (colors is not None and colors.device != dev):
         raise RuntimeError("simplify_vertex_clustering: tensors must live on one HIP device; there is no CPU path")
     V, F = int(verts.shape[0]), int(faces.shape[0])
-    L = _lib.lib()
     verts = verts.detach().contiguous()
     faces = faces.detach().to(torch.int64).contiguous()
     colors = None if colors is None else colors.detach().contiguous()
     i64 = dict(dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st = _lib.stream(dev)
         # the only values that visit the host: six bounds, the two extreme face indices, and the counts
         bounds = torch.cat([verts.amin(0), verts.amax(0)]).double().cpu().tolist()
         if F:
@@ -100,8 +99,8 @@ def simplify_vertex_clustering(verts, faces, colors=None, scale=64, voxel_size=N
             check_face_range(fmin, fmax, V)
         voxel, origin, dims = grid_parameters(bounds[:3], bounds[3:], scale, voxel_size)
         keys = torch.empty(V, **i64)
-        _lib.check(L.dm4d_simplify_vertex_keys(V, verts.data_ptr(), origin[0], origin[1], origin[2], voxel, dims[0], dims[1], dims[2],
-                                               keys.data_ptr(), st), "dm4d_simplify_vertex_keys")
+        _lib.call("dm4d_simplify_vertex_keys", V, verts.data_ptr(), origin[0], origin[1], origin[2], voxel, dims[0], dims[1], dims[2],
+                  keys.data_ptr(), st)
         sorted_keys, order = torch.sort(keys, stable=True)
         head = torch.ones(V, dtype=torch.bool, device=dev)
         head[1:] = sorted_keys[1:] != sorted_keys[:-1]
@@ -110,19 +109,17 @@ def simplify_vertex_clustering(verts, faces, colors=None, scale=64, voxel_size=N
         out_verts = torch.empty(C, 3, dtype=torch.float32, device=dev)
         out_colors = None if colors is None else torch.empty(C, 3, dtype=torch.float32, device=dev)
         vertex_cluster = torch.empty(V, **i64)
-        _lib.check(L.dm4d_simplify_cluster_average(V, C, order.data_ptr(), run_start.data_ptr(), verts.data_ptr(),
-                                                   None if colors is None else colors.data_ptr(), out_verts.data_ptr(),
-                                                   None if colors is None else out_colors.data_ptr(), vertex_cluster.data_ptr(), st),
-                   "dm4d_simplify_cluster_average")
+        _lib.call("dm4d_simplify_cluster_average", V, C, order.data_ptr(), run_start.data_ptr(), verts.data_ptr(),
+                  None if colors is None else colors.data_ptr(), out_verts.data_ptr(), None if colors is None else out_colors.data_ptr(),
+                  vertex_cluster.data_ptr(), st)
         canon = torch.empty(F, 3, **i64)
         key_bc = torch.empty(F, **i64)
-        _lib.check(L.dm4d_simplify_face_remap(F, V, C, faces.data_ptr(), vertex_cluster.data_ptr(), canon.data_ptr(), key_bc.data_ptr(), st),
-                   "dm4d_simplify_face_remap")
+        _lib.call("dm4d_simplify_face_remap", F, V, C, faces.data_ptr(), vertex_cluster.data_ptr(), canon.data_ptr(), key_bc.data_ptr(), st)
         # lexicographic order of the triples, equal triples in input order: stable sort by (b, c), then by a
         p1 = torch.sort(key_bc, stable=True).indices
         perm = p1[torch.sort(canon[:, 0][p1], stable=True).indices].contiguous()
         keep = torch.zeros(F, dtype=torch.uint8, device=dev)
-        _lib.check(L.dm4d_simplify_face_first(F, perm.data_ptr(), canon.data_ptr(), keep.data_ptr(), st), "dm4d_simplify_face_first")
+        _lib.call("dm4d_simplify_face_first", F, perm.data_ptr(), canon.data_ptr(), keep.data_ptr(), st)
         kept = keep.nonzero().flatten()                     # ascending: the input order of the first occurrences
         out_faces = canon[kept]
         n_degenerate = int((canon[:, 0] < 0).sum())

@@ -14,18 +14,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _p, stream as _st
 
 METHODS = {"lbs": 0, "dqs": 1, "hybrid": 2}
-GRAD_MODES = {"exact": 0, "pypose": 0x100}      # DM4D_GRAD_PYPOSE (include/dm4d.h): the reference's pypose autograd convention
+GRAD_MODES = {"exact": 0, "pypose": _lib.DM4D_GRAD_PYPOSE}      # (include/dm4d.h): the reference's pypose autograd convention
 DEFAULT_GRAD_MODE = "pypose"                    # what the reference trains with (DESIGN.md "gradient convention")
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _st(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _f32(t):
@@ -82,17 +75,15 @@ class MeshTopology:
 class _SkinVertices(torch.autograd.Function):
     @staticmethod
     def forward(ctx, graph, method, dx, dr, ds, do):
-        L = _lib.lib()
         g = graph
-        flags, method = method & 0x100, method & 0xff
+        flags, method = method & _lib.DM4D_GRAD_PYPOSE, method & 0xff
         dev = g.device
         dx_, dr_, ds_, do_ = _f32(dx), _f32(dr), _f32(ds), _f32(do)
         xyz = torch.empty(g.V, 3, dtype=torch.float32, device=dev)
         rot = torch.empty(g.V, 4, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_skin_vertices_forward(method, g.V, g.M, g.K, _p(g.verts), _p(g.nbr_idx), _p(g.nbr_w),
-                                                    _p(dx_), _p(dr_), _p(ds_), _p(do_), _p(xyz), _p(rot), _st(dev)),
-                       "dm4d_skin_vertices_forward")
+            _lib.call("dm4d_skin_vertices_forward", method, g.V, g.M, g.K, _p(g.verts), _p(g.nbr_idx), _p(g.nbr_w), _p(dx_), _p(dr_), _p(ds_),
+                      _p(do_), _p(xyz), _p(rot), _st(dev))
         ctx.graph, ctx.method = g, method | flags
         ctx.save_for_backward(dx_, dr_, *( [ds_] if ds_ is not None else []), *([do_] if do_ is not None else []))
         ctx.has = (ds_ is not None, do_ is not None)
@@ -115,10 +106,8 @@ class _SkinVertices(torch.autograd.Function):
         scratch = torch.empty(L.dm4d_skin_scratch_bytes(g.V, g.K), dtype=torch.uint8, device=dev)
         gx, gr = _f32(g_xyz), _f32(g_rot)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_skin_vertices_backward(method, g.V, g.M, g.K, _p(g.verts), _p(g.nbr_idx), _p(g.nbr_w),
-                                                     _p(dx_), _p(dr_), _p(ds_), _p(do_), _p(gx), _p(gr),
-                                                     _p(g.csr_off), _p(g.csr_items), _p(scratch), _p(o_dx), _p(o_dr),
-                                                     _p(o_ds), _p(o_do), _st(dev)), "dm4d_skin_vertices_backward")
+            _lib.call("dm4d_skin_vertices_backward", method, g.V, g.M, g.K, _p(g.verts), _p(g.nbr_idx), _p(g.nbr_w), _p(dx_), _p(dr_), _p(ds_),
+                      _p(do_), _p(gx), _p(gr), _p(g.csr_off), _p(g.csr_items), _p(scratch), _p(o_dx), _p(o_dr), _p(o_ds), _p(o_do), _st(dev))
         s = ctx.shapes
         return (None, None, o_dx.reshape(s[0]), o_dr.reshape(s[1]), None if o_ds is None else o_ds.reshape(s[2]),
                 None if o_do is None else o_do.reshape(s[3]))
@@ -139,7 +128,6 @@ def skin_vertices(graph: DeformGraph, dx, dr, ds=None, d_opacity=None, method="h
 class _FaceGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, topo, vxyz, vrot, q_static, want_normals, flags):
-        L = _lib.lib()
         t = topo
         dev = t.device
         vx, vr, qs = _f32(vxyz), _f32(vrot), _f32(q_static)
@@ -148,8 +136,7 @@ class _FaceGaussians(torch.autograd.Function):
         means, rots = torch.empty(N, 3, **f), torch.empty(N, 4, **f)
         normals = torch.empty(N, 3, **f) if want_normals else None
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_face_gaussians_forward(t.F, t.G, _p(t.faces), _p(vx), _p(vr), _p(qs), _p(means), _p(rots),
-                                                     _p(normals), _st(dev)), "dm4d_face_gaussians_forward")
+            _lib.call("dm4d_face_gaussians_forward", t.F, t.G, _p(t.faces), _p(vx), _p(vr), _p(qs), _p(means), _p(rots), _p(normals), _st(dev))
         ctx.topo, ctx.flags = t, flags
         ctx.save_for_backward(vx, vr, qs)
         if normals is None:
@@ -168,9 +155,8 @@ class _FaceGaussians(torch.autograd.Function):
         gm, gr = _f32(g_means), _f32(g_rots)
         gn = _f32(g_normals) if g_normals is not None and g_normals.numel() else None
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_face_gaussians_backward(t.F, t.G | ctx.flags, t.V, _p(t.faces), _p(vx), _p(vr), _p(qs), _p(gm), _p(gr),
-                                                      _p(gn), _p(t.csr_off), _p(t.csr_items), _p(scratch), _p(o_x),
-                                                      _p(o_r), _st(dev)), "dm4d_face_gaussians_backward")
+            _lib.call("dm4d_face_gaussians_backward", t.F, t.G | ctx.flags, t.V, _p(t.faces), _p(vx), _p(vr), _p(qs), _p(gm), _p(gr), _p(gn),
+                      _p(t.csr_off), _p(t.csr_items), _p(scratch), _p(o_x), _p(o_r), _st(dev))
         return None, o_x, o_r, None, None, None
 
 
@@ -189,7 +175,7 @@ class _MatrixPypose(torch.autograd.Function):
             qc = _f32(q)
             R = torch.empty(qc.shape[:-1] + (3, 3), dtype=torch.float32, device=q.device)
             with torch.cuda.device(q.device):
-                _lib.check(_lib.lib().dm4d_quat_to_matrix_forward(qc.numel() // 4, _p(qc), _p(R), _st(q.device)), "dm4d_quat_to_matrix_forward")
+                _lib.call("dm4d_quat_to_matrix_forward", qc.numel() // 4, _p(qc), _p(R), _st(q.device))
         else:
             x, y, z, w = q.unbind(-1)
             R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
@@ -205,8 +191,7 @@ class _MatrixPypose(torch.autograd.Function):
             Gc = _f32(G)
             gq = torch.empty(R.shape[:-2] + (4,), dtype=torch.float32, device=R.device)
             with torch.cuda.device(R.device):
-                _lib.check(_lib.lib().dm4d_quat_to_matrix_backward_pypose(R.numel() // 9, _p(R), _p(Gc), _p(gq), _st(R.device)),
-                           "dm4d_quat_to_matrix_backward_pypose")
+                _lib.call("dm4d_quat_to_matrix_backward_pypose", R.numel() // 9, _p(R), _p(Gc), _p(gq), _st(R.device))
             return gq
         t = torch.linalg.cross(R.transpose(-1, -2), G.transpose(-1, -2), dim=-1).sum(dim=-2)     # sum over the columns i
         return torch.cat([t, torch.zeros_like(t[..., :1])], dim=-1)
@@ -246,8 +231,7 @@ class _VertexScales(torch.autograd.Function):
         NF = int(ds_.shape[0])
         out = torch.empty(NF, g.V, 3, 3, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_vertex_scales_forward(m, NF, g.V, g.M, g.K, _p(g.nbr_idx), _p(g.nbr_w), _p(ds_), _p(do_), _p(out), _st(dev)),
-                       "dm4d_vertex_scales_forward")
+            _lib.call("dm4d_vertex_scales_forward", m, NF, g.V, g.M, g.K, _p(g.nbr_idx), _p(g.nbr_w), _p(ds_), _p(do_), _p(out), _st(dev))
         ctx.graph, ctx.m = g, m
         ctx.save_for_backward(ds_, do_)
         return out
@@ -261,8 +245,8 @@ class _VertexScales(torch.autograd.Function):
         o_ds = torch.empty_like(ds_)
         o_do = torch.empty_like(do_) if do_ is not None else None
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_vertex_scales_backward(ctx.m, NF, g.V, g.M, g.K, _p(g.nbr_idx), _p(g.nbr_w), _p(ds_), _p(do_), _p(g.csr_off),
-                                                     _p(g.csr_items), _p(go), _p(o_ds), _p(o_do), _st(dev)), "dm4d_vertex_scales_backward")
+            _lib.call("dm4d_vertex_scales_backward", ctx.m, NF, g.V, g.M, g.K, _p(g.nbr_idx), _p(g.nbr_w), _p(ds_), _p(do_), _p(g.csr_off),
+                      _p(g.csr_items), _p(go), _p(o_ds), _p(o_do), _st(dev))
         return None, None, o_ds, o_do
 
 
@@ -292,8 +276,7 @@ class _GaussianScales(torch.autograd.Function):
         NF = int(sv.shape[0])
         out = torch.empty(NF, t.F * t.G, 3, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_gaussian_scales_forward(NF, t.F, t.G, t.V, _p(t.faces), _p(bary), _p(sv), _p(sc), _p(out), _st(dev)),
-                       "dm4d_gaussian_scales_forward")
+            _lib.call("dm4d_gaussian_scales_forward", NF, t.F, t.G, t.V, _p(t.faces), _p(bary), _p(sv), _p(sc), _p(out), _st(dev))
         ctx.topo, ctx.bary, ctx.sc_shape = t, bary, scaling.shape
         ctx.save_for_backward(sv, sc)
         return out
@@ -307,8 +290,8 @@ class _GaussianScales(torch.autograd.Function):
         o_sv = torch.empty_like(sv) if ctx.needs_input_grad[2] else None
         o_sc = torch.empty_like(sc) if ctx.needs_input_grad[3] else None
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_gaussian_scales_backward(NF, t.F, t.G, t.V, _p(t.faces), _p(ctx.bary), _p(sv), _p(sc), _p(t.csr_off), _p(t.csr_items),
-                                                       _p(go), _p(o_sv), _p(o_sc), _st(dev)), "dm4d_gaussian_scales_backward")
+            _lib.call("dm4d_gaussian_scales_backward", NF, t.F, t.G, t.V, _p(t.faces), _p(ctx.bary), _p(sv), _p(sc), _p(t.csr_off), _p(t.csr_items),
+                      _p(go), _p(o_sv), _p(o_sc), _st(dev))
         return None, None, o_sv, None if o_sc is None else o_sc.reshape(ctx.sc_shape)
 
 

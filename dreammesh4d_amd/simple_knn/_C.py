@@ -18,11 +18,11 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
     out = torch.empty(p.shape[0], dtype=torch.float32, device=p.device)
     n = int(p.shape[0])
     with torch.cuda.device(p.device):
-        st = torch.cuda.current_stream(p.device).cuda_stream
+        st = _lib.stream(p.device)
         if n <= BRUTE_FORCE_MAX:       # exhaustive LDS-tiled search: no scratch, fastest for small clouds
-            _lib.check(L.dm4d_dist2_knn3(n, p.data_ptr() if n else None, out.data_ptr() if n else None, st), "dm4d_dist2_knn3")
+            _lib.call("dm4d_dist2_knn3", n, p.data_ptr() if n else None, out.data_ptr() if n else None, st)
         else:                          # Morton-ordered 1024-point boxes (upstream's structure): same values, O(N) boxes visited
             nbytes = L.dm4d_knn_scratch_bytes(n)
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
-            _lib.check(L.dm4d_dist2_knn3_ws(n, p.data_ptr(), out.data_ptr(), scratch.data_ptr(), nbytes, st), "dm4d_dist2_knn3_ws")
+            _lib.call("dm4d_dist2_knn3_ws", n, p.data_ptr(), out.data_ptr(), scratch.data_ptr(), nbytes, st)
     return out

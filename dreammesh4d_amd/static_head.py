@@ -23,10 +23,9 @@ class _StaticHead(torch.autograd.Function):
         partial = torch.empty(B * nb, 8, dtype=torch.float32, device=dev)
         half = torch.empty(n_rnd, H // 2, W // 2, 3, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_static_head_forward(B, H, W, c.data_ptr(), d.data_ptr(), a.data_ptr(), ref_pos.data_ptr(), rnd_pos.data_ptr(),
-                                                  ref_images.data_ptr(), ref_masks.data_ptr(), fidx_ref.data_ptr(), n_ref, n_rnd,
-                                                  partial.data_ptr(), half.data_ptr() if n_rnd else 0,
-                                                  torch.cuda.current_stream(dev).cuda_stream), "dm4d_static_head_forward")
+            _lib.call("dm4d_static_head_forward", B, H, W, c.data_ptr(), d.data_ptr(), a.data_ptr(), ref_pos.data_ptr(), rnd_pos.data_ptr(),
+                      ref_images.data_ptr(), ref_masks.data_ptr(), fidx_ref.data_ptr(), n_ref, n_rnd, partial.data_ptr(),
+                      half.data_ptr() if n_rnd else 0, _lib.stream(dev))
         ctx.save_for_backward(c, d, a, ref_pos, rnd_pos, ref_images, ref_masks, fidx_ref)
         ctx.n = (n_ref, n_rnd)
         from .loss_sum import partial_sums
@@ -35,7 +34,6 @@ class _StaticHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_terms, g_half):
-        L = _lib.lib()
         c, d, a, ref_pos, rnd_pos, ref_images, ref_masks, fidx_ref = ctx.saved_tensors
         n_ref, n_rnd = ctx.n
         B, C, H, W = c.shape
@@ -44,10 +42,9 @@ class _StaticHead(torch.autograd.Function):
         gt = torch.zeros(5, dtype=torch.float32, device=dev) if g_terms is None else g_terms.detach().to(torch.float32).contiguous()
         gh = None if g_half is None else g_half.detach().to(torch.float32).contiguous()
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_static_head_backward(B, H, W, c.data_ptr(), d.data_ptr(), a.data_ptr(), ref_pos.data_ptr(), rnd_pos.data_ptr(),
-                                                   ref_images.data_ptr(), ref_masks.data_ptr(), fidx_ref.data_ptr(), n_ref, n_rnd,
-                                                   gt.data_ptr(), 0 if gh is None or not n_rnd else gh.data_ptr(), gc.data_ptr(), gd.data_ptr(),
-                                                   ga.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "dm4d_static_head_backward")
+            _lib.call("dm4d_static_head_backward", B, H, W, c.data_ptr(), d.data_ptr(), a.data_ptr(), ref_pos.data_ptr(), rnd_pos.data_ptr(),
+                      ref_images.data_ptr(), ref_masks.data_ptr(), fidx_ref.data_ptr(), n_ref, n_rnd, gt.data_ptr(),
+                      0 if gh is None or not n_rnd else gh.data_ptr(), gc.data_ptr(), gd.data_ptr(), ga.data_ptr(), _lib.stream(dev))
         return gc, gd, ga, None, None, None, None, None, None, None, None
 
 

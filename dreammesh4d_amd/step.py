@@ -27,12 +27,9 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 from .geometry import reject_sh_coefficients
 from . import hexplane as hx
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 def _on(t, dev):
@@ -174,7 +171,7 @@ class DynamicStep:
         v.vxyz, v.vrot, v.means3D, v.rotations, v.colors, v.radii = (_p(o[k]) for k in ("vxyz", "vrot", "means", "rots", "colors", "radii"))
         v.out_color, v.out_depth, v.out_alpha = _p(o["color"]), _p(o["depth"]), _p(o["alpha"])
         v.geom, v.binning, v.image = _p(ws["geom"]), _p(ws["binning"]), _p(ws["image"])
-        v.n_frames, v.scales_per_frame, v.record_mode = NF, 0, 0
+        v.n_frames, v.scales_per_frame, v.record_mode = NF, 0, _lib.DM4D_RECORDS_CELL
         gr = d.grads
         gr.node_csr_offsets, gr.node_csr_items, gr.vert_csr_offsets, gr.vert_csr_items = _p(g.csr_off), _p(g.csr_items), _p(t.csr_off), _p(t.csr_items)
         gr.grad_scratch, gr.skin_scratch, gr.face_scratch = _p(ws["grad"]), _p(ws["skin"]), _p(ws["face"])
@@ -188,8 +185,8 @@ class DynamicStep:
         gr.dL_dds = _p(gnode["ds"]) if v.ds else None
         gr.dL_ddo = _p(gnode["do"]) if v.d_opacity else None
         d.S = S
-        d.hex_flags = hx.plane_layout(pl) | 4            # DM4D_HEX_CHANNELS_LAST?, DM4D_HEX_TIMES_01
-        d.hex_backward_flags = 2                         # DM4D_HEX_KEEP_SPATIAL: persistent gradient planes
+        d.hex_flags = hx.plane_layout(pl) | _lib.DM4D_HEX_TIMES_01
+        d.hex_backward_flags = _lib.DM4D_HEX_KEEP_SPATIAL         # persistent gradient planes
         d.res, d.aabb_host = self.plan.res_c, self.plan.aabb_c
         self._pp = hx._plane_ptr_array(pl)
         self._gp = hx._plane_ptr_array(self.g_planes)
@@ -216,7 +213,7 @@ class DynamicStep:
             L.dm4d_step_destroy(self.handle)
             self.handle = None
         h = C.c_void_p()
-        _lib.check(L.dm4d_step_create(C.byref(d), C.byref(h)), "dm4d_step_create")
+        _lib.call("dm4d_step_create", C.byref(d), C.byref(h))
         self.handle = h
         self.key = self._ptr_state()
         self._views = C.cast(L.dm4d_step_views(h), C.POINTER(_lib.ViewsStruct))
@@ -250,8 +247,7 @@ class DynamicStep:
         self.serial += 1
         self._keep = (times, vm, pm, fidx)        # the library reads them again in the backward
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().dm4d_step_forward(self.handle, times.data_ptr(), vm.data_ptr(), pm.data_ptr(), _p(fidx),
-                                                    torch.cuda.current_stream(dev).cuda_stream), "dm4d_step_forward")
+            _lib.call("dm4d_step_forward", self.handle, times.data_ptr(), vm.data_ptr(), pm.data_ptr(), _p(fidx), _lib.stream(dev))
         self.r.last = self._last
 
     def _backward(self, g_color, g_depth, g_alpha, g_vxyz, g_vrot):
@@ -267,11 +263,9 @@ class DynamicStep:
         with torch.cuda.device(dev):
             if bool(getattr(self.r, "rgb_gradient_only", False)) and gd is None and self.r.deterministic:
                 # no loss reads the normal image: channels 3..5 of the upstream gradient are not read (views.py, dm4d_views_backward_rgb)
-                _lib.check(_lib.lib().dm4d_step_backward_rgb(self.handle, gc.data_ptr(), _p(ga), _p(gx), _p(gr_),
-                                                             torch.cuda.current_stream(dev).cuda_stream), "dm4d_step_backward_rgb")
+                _lib.call("dm4d_step_backward_rgb", self.handle, gc.data_ptr(), _p(ga), _p(gx), _p(gr_), _lib.stream(dev))
             else:
-                _lib.check(_lib.lib().dm4d_step_backward(self.handle, gc.data_ptr(), _p(gd), _p(ga), _p(gx), _p(gr_),
-                                                         torch.cuda.current_stream(dev).cuda_stream), "dm4d_step_backward")
+                _lib.call("dm4d_step_backward", self.handle, gc.data_ptr(), _p(gd), _p(ga), _p(gx), _p(gr_), _lib.stream(dev))
         for p, gb in zip(self.planes, self.g_planes):
             if p.requires_grad:
                 p.grad = gb

@@ -47,7 +47,6 @@ class _SugarAttributes(torch.autograd.Function):
     def forward(ctx, points, cx, log_scales, densities, sh_dc, faces, bary, thickness, clip):
         from . import _lib
 
-        L = _lib.lib()
         dev = points.device
         Fn, G, V = int(faces.shape[0]), int(bary.shape[0]), int(points.shape[0])
         N = Fn * G
@@ -56,10 +55,9 @@ class _SugarAttributes(torch.autograd.Function):
         b = bary.detach().reshape(G, 3).to(torch.float32).contiguous()
         args = tuple(t.detach() for t in (points, cx, log_scales, densities, sh_dc))
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_sugar_attributes_forward(Fn, G, V, args[0].data_ptr(), faces.data_ptr(), b.data_ptr(), args[1].data_ptr(),
-                                                       args[2].data_ptr(), args[3].data_ptr(), args[4].data_ptr(), float(thickness), float(clip),
-                                                       *[o.data_ptr() for o in out], torch.cuda.current_stream(dev).cuda_stream),
-                       "dm4d_sugar_attributes_forward")
+            _lib.call("dm4d_sugar_attributes_forward", Fn, G, V, args[0].data_ptr(), faces.data_ptr(), b.data_ptr(), args[1].data_ptr(),
+                      args[2].data_ptr(), args[3].data_ptr(), args[4].data_ptr(), float(thickness), float(clip), *[o.data_ptr() for o in out],
+                      _lib.stream(dev))
         ctx.save_for_backward(*args, faces, b, out[2], out[3])
         ctx.consts = (Fn, G, V, float(thickness), float(clip))
         ctx.set_materialize_grads(False)
@@ -69,7 +67,6 @@ class _SugarAttributes(torch.autograd.Function):
     def backward(ctx, g_m, g_q, g_s, g_o, g_c):
         from . import _lib
 
-        L = _lib.lib()
         points, cx, ls, den, sh, faces, b, scales, opac = ctx.saved_tensors
         Fn, G, V, thickness, clip = ctx.consts
         dev = points.device
@@ -79,10 +76,9 @@ class _SugarAttributes(torch.autograd.Function):
         g_m, g_q, g_s, g_o, g_c = c(g_m), c(g_q), c(g_s), c(g_o), c(g_c)
         out = [torch.empty_like(t) if n else None for t, n in zip((points, cx, ls, den, sh), need[:5])]
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_sugar_attributes_backward(Fn, G, V, points.data_ptr(), faces.data_ptr(), b.data_ptr(), cx.data_ptr(), ls.data_ptr(),
-                                                        den.data_ptr(), sh.data_ptr(), thickness, clip, scales.data_ptr(), opac.data_ptr(),
-                                                        p(g_m), p(g_q), p(g_s), p(g_o), p(g_c), *[p(o) for o in out],
-                                                        torch.cuda.current_stream(dev).cuda_stream), "dm4d_sugar_attributes_backward")
+            _lib.call("dm4d_sugar_attributes_backward", Fn, G, V, points.data_ptr(), faces.data_ptr(), b.data_ptr(), cx.data_ptr(), ls.data_ptr(),
+                      den.data_ptr(), sh.data_ptr(), thickness, clip, scales.data_ptr(), opac.data_ptr(), p(g_m), p(g_q), p(g_s), p(g_o), p(g_c),
+                      *[p(o) for o in out], _lib.stream(dev))
         return (*out, None, None, None, None)
 
 

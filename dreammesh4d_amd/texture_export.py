@@ -15,7 +15,6 @@ After training, the reference bakes ONE texture of the canonical surface mesh an
 ROCm build; its conventions are restated in csrc/texbake.hip.  Where they could not be checked against pytorch3d (edge coverage,
 the float arithmetic of the nearest sample) the parity is unpinned.  Everything on the device is HIP; there is no CPU path.
 """
-import ctypes as C
 import math
 import os
 from dataclasses import dataclass
@@ -25,19 +24,13 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, gviews
+from ._lib import ptr as _p, stream as _stream
+from .ops import _f32
 from .renderer import cam_info_gaussian
 
 SH_C0 = 0.28209479177387814
 N_PREDICT_VIEWS = 120
 PREDICT_RESOLUTION = 1024
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 @dataclass
@@ -101,10 +94,6 @@ def _i32(t):
     return t.to(torch.int32).contiguous()
 
 
-def _f32(t):
-    return t.detach().to(torch.float32).contiguous()
-
-
 def build_atlas(geometry, square_size=20) -> Atlas:
     """Atlas and SH-initialised texture of the geometry's canonical surface mesh (``on_predict_start``, C/system/base.py:72-209).
     `geometry`: ``sugar.SuGaR`` or ``sugar.DynamicSuGaR`` on the HIP device."""
@@ -128,8 +117,8 @@ def build_atlas(geometry, square_size=20) -> Atlas:
         raise ValueError("build_atlas: the geometry's Gaussians are not F x G")
     texture = torch.full((T, T, 3), 0.5, dtype=torch.float32, device=dev)        # SH2RGB of the reference's zero image
     with torch.cuda.device(dev):
-        _lib.check(L.dm4d_tex_atlas_init(Fn, G, int(square_size), _p(verts), _p(faces), _p(means), _p(rot), _p(scales), _p(dc),
-                                         _p(texture), _stream(dev)), "dm4d_tex_atlas_init")
+        _lib.call("dm4d_tex_atlas_init", Fn, G, int(square_size), _p(verts), _p(faces), _p(means), _p(rot), _p(scales), _p(dc), _p(texture),
+                  _stream(dev))
     faces_uv, verts_uv = atlas_uv(Fn, int(square_size), dev)
     return Atlas(faces_uv, verts_uv, T, texture)
 
@@ -214,22 +203,20 @@ class TextureBaker:
         face = torch.empty(B, H, W, dtype=torch.int32, device=dev) if with_faces else None
         bary = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev) if with_faces else None
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_mesh_raster(B, H, W, self.F, _p(self.verts), _p(self.faces), _p(vm), _p(pm), _p(self.verts_uv), _p(self.faces_uv),
-                                          self.T, _p(self._scratch), self._scratch.numel(), _p(texel), _p(face), _p(bary), _stream(dev)),
-                       "dm4d_mesh_raster")
+            _lib.call("dm4d_mesh_raster", B, H, W, self.F, _p(self.verts), _p(self.faces), _p(vm), _p(pm), _p(self.verts_uv), _p(self.faces_uv),
+                      self.T, _p(self._scratch), self._scratch.numel(), _p(texel), _p(face), _p(bary), _stream(dev))
         return (texel, face, bary) if with_faces else texel
 
     def accumulate(self, texel, rgb):
         """One view: texel [H,W] int32, rgb [3,H,W] float32 (both on the device)."""
-        L = _lib.lib()
         texel, rgb = texel.to(torch.int32).contiguous(), _f32(rgb)
         n = int(texel.numel())
         if texel.dim() != 2 or tuple(rgb.shape) != (3, *texel.shape):
             raise ValueError(f"TextureBaker.accumulate: rgb must be [3,H,W] for a texel map {tuple(texel.shape)}, got {tuple(rgb.shape)}")
         self.epoch += 1
         with torch.cuda.device(self.device):
-            _lib.check(L.dm4d_tex_accumulate(n, _p(texel), _p(rgb), n, self.epoch, _p(self.claim), self.claim.numel() * 8, self.T * self.T,
-                                             _p(self.sum), _p(self.count), _stream(self.device)), "dm4d_tex_accumulate")
+            _lib.call("dm4d_tex_accumulate", n, _p(texel), _p(rgb), n, self.epoch, _p(self.claim), self.claim.numel() * 8, self.T * self.T,
+                      _p(self.sum), _p(self.count), _stream(self.device))
 
     def add_views(self, rgb, viewmats, projmats):
         texel = self.rasterize(viewmats, projmats)

@@ -13,21 +13,14 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 from .geometry import reject_sh_coefficients
-from .ops import DEFAULT_GRAD_MODE, GRAD_MODES, METHODS, DeformGraph, MeshTopology
+from .ops import DEFAULT_GRAD_MODE, GRAD_MODES, METHODS, DeformGraph, MeshTopology, _f32
 
 vp = C.c_void_p
 
 
 ViewsStruct, ViewsGrads = _lib.ViewsStruct, _lib.ViewsGrads
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _f32(t):
-    return None if t is None else t.detach().to(torch.float32).contiguous()
 
 
 class ViewRenderer:
@@ -152,15 +145,13 @@ class ViewRenderer:
         on overflow after enlarging the capacity for subsequent calls."""
         if self.last is None:
             return None
-        L = _lib.lib()
         vs, _ = self.last
         B = vs.B
         nr = (C.c_int64 * B)()
         nrec = (C.c_int64 * B)()
         ov = (C.c_int32 * B)()
         with torch.cuda.device(self.device):
-            _lib.check(L.dm4d_views_counters(C.byref(vs), nr, nrec, ov,
-                                             torch.cuda.current_stream(self.device).cuda_stream), "dm4d_views_counters")
+            _lib.call("dm4d_views_counters", C.byref(vs), nr, nrec, ov, _lib.stream(self.device))
         nr, nrec = list(nr), list(nrec)
         self.last_num_records = nrec
         if any(o & 1 for o in ov):
@@ -179,7 +170,6 @@ class ViewRenderer:
 class _RenderViews(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r, dx, dr, ds, do, q_static, scales, opacities, rgb, viewmats, projmats, bg6, frame_index, means2D):
-        L = _lib.lib()
         g, t, dev = r.graph, r.topo, r.device
         B = int(viewmats.shape[0])
         N, H, W = r.N, r.H, r.W
@@ -210,11 +200,10 @@ class _RenderViews(torch.autograd.Function):
                          _p(keep["sc"]), _p(keep["op"]), _p(keep["rgb"]), _p(out["vxyz"]), _p(out["vrot"]),
                          _p(out["means"]), _p(out["rots"]), _p(out["colors"]), _p(out["radii"]), _p(out["color"]),
                          _p(out["depth"]), _p(out["alpha"]), _p(ws["geom"]), _p(ws["binning"]), _p(ws["image"]), _p(fidx), NF,
-                         1 if sc_per_frame else 0, 0 if r.deterministic else 1)
+                         1 if sc_per_frame else 0, _lib.DM4D_RECORDS_CELL if r.deterministic else _lib.DM4D_RECORDS_TILE)
         keep["fidx"] = fidx
         with torch.cuda.device(dev):
-            _lib.check(L.dm4d_views_forward(C.byref(vs), torch.cuda.current_stream(dev).cuda_stream),
-                       "dm4d_views_forward")
+            _lib.call("dm4d_views_forward", C.byref(vs), _lib.stream(dev))
         # Tensors RETURNED from forward must not be kept as plain ctx attributes: output -> grad_fn -> ctx -> output is
         # a reference cycle through C++ that the Python GC cannot break (it leaked every step's graph: ~150 MB per
         # step).  They go through save_for_backward; only the internal buffers stay on ctx.
@@ -232,7 +221,6 @@ class _RenderViews(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_color, g_depth, g_alpha, _g_radii, g_vxyz, g_vrot):
-        L = _lib.lib()
         r, vs = ctx.r, ctx.vs
         if ctx.ws is None:
             raise RuntimeError("render_views: backward called a second time (retain_graph): the rasterizer workspaces of "
@@ -263,10 +251,8 @@ class _RenderViews(torch.autograd.Function):
         # gradient is not read and the blend backward carries 5 per-entry sums instead of 8 (dm4d_views_backward_rgb) -- where the lean
         # configuration it needs applies (static appearance frozen, no depth gradient, cell records); otherwise the full call
         rgb = bool(getattr(r, "rgb_gradient_only", False)) and not ctx.need_static and gd is None and r.deterministic
-        fn = L.dm4d_views_backward_rgb if rgb else L.dm4d_views_backward
         with torch.cuda.device(dev):
-            _lib.check(fn(C.byref(vs), C.byref(gs), torch.cuda.current_stream(dev).cuda_stream),
-                       "dm4d_views_backward_rgb" if rgb else "dm4d_views_backward")
+            _lib.call("dm4d_views_backward_rgb" if rgb else "dm4d_views_backward", C.byref(vs), C.byref(gs), _lib.stream(dev))
         s = ctx.shapes
         r._give_ws(ctx.ws)   # stream-ordered reuse by the next forward is safe
         ctx.ws = ctx.internal = None

@@ -924,29 +924,25 @@ class TemporalStableZero123Guidance(nn.Module):
 
             from . import _lib
 
-            L = _lib.lib()
             ptr = lambda v: C_.c_void_p(v.data_ptr())
             strides = lambda v: (C_.c_int64 * 4)(*v.stride())
-            stream = torch.cuda.current_stream(dev).cuda_stream
+            stream = _lib.stream(dev)
             unet = self.model.model.diffusion_model
             pre, ctx = (None, None) if st.pre is None else st.pre       # (the conditioning graph's static results, run_pre)
             moments = self.model.first_stage_model.encode_moments((st.imgs * 2.0 - 1.0).to(dt))
             with torch.no_grad():
                 x_in = torch.empty(2 * B, 8, 32, 32, device=dev, dtype=dt, memory_format=torch.channels_last)
                 t2 = torch.empty(2 * B, dtype=torch.long, device=dev)
-                _lib.check(L.dm4d_sds_prepare(B, 32, 32, float(self.model.scale_factor), ptr(moments), strides(moments), ptr(st.post),
-                                              strides(st.post), ptr(st.noise), strides(st.noise), ptr(st.latents), strides(st.latents),
-                                              ptr(st.t), ptr(self.alphas), ptr(self.c_concat), strides(self.c_concat),
-                                              ptr(st.fidx), ptr(x_in), strides(x_in), ptr(t2), stream), "dm4d_sds_prepare")
+                _lib.call("dm4d_sds_prepare", B, 32, 32, float(self.model.scale_factor), ptr(moments), strides(moments), ptr(st.post),
+                          strides(st.post), ptr(st.noise), strides(st.noise), ptr(st.latents), strides(st.latents), ptr(st.t), ptr(self.alphas),
+                          ptr(self.c_concat), strides(self.c_concat), ptr(st.fidx), ptr(x_in), strides(x_in), ptr(t2), stream)
                 pred = unet(x_in, t2, context=self._crossattn_from_T(st.T, st.fidx) if ctx is None else ctx, pre=pre)
                 d_mom = torch.empty(moments.shape, device=dev, dtype=dt)      # (contiguous, like the `cat` autograd builds there: the library picks the
                                                                               #  quant_conv's backward kernel by the gradient's layout)
                 loss, gnorm = torch.empty((), device=dev), torch.empty((), device=dev)
-                _lib.check(L.dm4d_sds_finish(B, 32, 32, float(self.model.scale_factor), float(scale), ptr(pred), strides(pred),
-                                             ptr(st.latents), strides(st.latents), ptr(st.noise), strides(st.noise), ptr(st.t),
-                                             ptr(self.alphas), ptr(st.clip) if clipped else None, ptr(moments),
-                                             strides(moments), ptr(st.post), strides(st.post), ptr(d_mom), strides(d_mom), ptr(loss),
-                                             ptr(gnorm), stream), "dm4d_sds_finish")
+                _lib.call("dm4d_sds_finish", B, 32, 32, float(self.model.scale_factor), float(scale), ptr(pred), strides(pred), ptr(st.latents),
+                          strides(st.latents), ptr(st.noise), strides(st.noise), ptr(st.t), ptr(self.alphas), ptr(st.clip) if clipped else None,
+                          ptr(moments), strides(moments), ptr(st.post), strides(st.post), ptr(d_mom), strides(d_mom), ptr(loss), ptr(gnorm), stream)
             (d_imgs,) = torch.autograd.grad(moments, st.imgs, grad_outputs=d_mom)
             return loss, gnorm, d_imgs
 

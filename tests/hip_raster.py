@@ -6,10 +6,7 @@ import numpy as np
 import torch
 
 from dreammesh4d_amd import _lib
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
+from dreammesh4d_amd._lib import ptr as _p
 
 
 class HipRaster:
@@ -42,15 +39,14 @@ class HipRaster:
         self.radii = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
         gb = L.dm4d_raster_geom_bytes(N, H, W)
         self.geom = torch.empty(gb, dtype=torch.uint8, device=dev)
-        _lib.check(L.dm4d_rasterize_prepare(self.settings, self.inputs, _p(self.radii), _p(self.geom), gb, st), "prepare")
-        self.D = _lib.check(L.dm4d_rasterize_num_rendered(_p(self.geom), st), "num_rendered")
-        self.R = _lib.check(L.dm4d_rasterize_num_records(_p(self.geom), st), "num_records")
+        _lib.call("dm4d_rasterize_prepare", self.settings, self.inputs, _p(self.radii), _p(self.geom), gb, st)
+        self.D = _lib.call("dm4d_rasterize_num_rendered", _p(self.geom), st)
+        self.R = _lib.call("dm4d_rasterize_num_records", _p(self.geom), st)
         self.cap = self.D if capacity is None else capacity
         self.binning = torch.empty(L.dm4d_raster_binning_bytes(self.cap), dtype=torch.uint8, device=dev)
         self.image = torch.empty(L.dm4d_raster_image_bytes(H, W), dtype=torch.uint8, device=dev)
-        _lib.check(L.dm4d_rasterize_render(self.settings, self.inputs, _p(self.radii), _p(self.geom), _p(self.binning),
-                                           self.cap, _p(self.image), _p(self.color), _p(self.depth), _p(self.alpha),
-                                           st), "render")
+        _lib.call("dm4d_rasterize_render", self.settings, self.inputs, _p(self.radii), _p(self.geom), _p(self.binning), self.cap, _p(self.image),
+                  _p(self.color), _p(self.depth), _p(self.alpha), st)
         torch.cuda.synchronize(dev)
         return self.color.cpu().numpy(), self.radii[:N].cpu().numpy(), self.depth.cpu().numpy(), self.alpha.cpu().numpy()
 
@@ -67,13 +63,12 @@ class HipRaster:
              "ranges": np.zeros((T, 2), np.uint32), "n_contrib": np.zeros((H, W), np.uint32),
              "final_T": np.zeros((H, W), np.float32)}
         f = lambda a, ty: a.ctypes.data_as(ty)
-        _lib.check(L.dm4d_raster_read_geom(_p(self.geom), N, H, W, f(s["xy"], _lib.c_f), f(s["depths"], _lib.c_f),
-                                           f(s["conic_opacity"], _lib.c_f), f(s["tiles_touched"], _lib.c_u32), st))
-        _lib.check(L.dm4d_raster_read_sorted(_p(self.geom), _p(self.binning), N, H, W, min(self.D, self.cap),
-                                             f(s["keys"], _lib.c_u64), f(s["values"], _lib.c_u32),
-                                             f(s["ranges"], _lib.c_u32), st))
-        _lib.check(L.dm4d_raster_read_image_state(_p(self.geom), _p(self.binning), _p(self.image), N, H, W, self.cap,
-                                                  f(s["n_contrib"], _lib.c_u32), f(s["final_T"], _lib.c_f), st))
+        _lib.call("dm4d_raster_read_geom", _p(self.geom), N, H, W, f(s["xy"], _lib.c_f), f(s["depths"], _lib.c_f), f(s["conic_opacity"], _lib.c_f),
+                  f(s["tiles_touched"], _lib.c_u32), st)
+        _lib.call("dm4d_raster_read_sorted", _p(self.geom), _p(self.binning), N, H, W, min(self.D, self.cap), f(s["keys"], _lib.c_u64),
+                  f(s["values"], _lib.c_u32), f(s["ranges"], _lib.c_u32), st)
+        _lib.call("dm4d_raster_read_image_state", _p(self.geom), _p(self.binning), _p(self.image), N, H, W, self.cap, f(s["n_contrib"], _lib.c_u32),
+                  f(s["final_T"], _lib.c_f), st)
         for k in ("xy", "depths", "conic_opacity", "tiles_touched"):
             s[k] = s[k][:N]
         s["keys"], s["values"] = s["keys"][:self.D], s["values"][:self.D]
@@ -92,10 +87,8 @@ class HipRaster:
         rcap = self.R if record_capacity is None else record_capacity
         grad = torch.empty(L.dm4d_raster_grad_bytes(rcap, self.C), dtype=torch.uint8, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.dm4d_rasterize_backward(self.settings, self.inputs, _p(self.radii), _p(self.geom),
-                                             _p(self.binning), self.cap, _p(self.image), _p(grad), rcap, _p(gC), _p(gD),
-                                             _p(gA), _p(o["dL_dmeans2D"]), _p(o["dL_dmeans3D"]), _p(o["dL_dopacity"]),
-                                             _p(o["dL_dcolors"]), _p(o["dL_dsh"]), _p(o["dL_dscales"]),
-                                             _p(o["dL_drots"]), _p(o["dL_dcov3D"]), st), "backward")
+        _lib.call("dm4d_rasterize_backward", self.settings, self.inputs, _p(self.radii), _p(self.geom), _p(self.binning), self.cap, _p(self.image),
+                  _p(grad), rcap, _p(gC), _p(gD), _p(gA), _p(o["dL_dmeans2D"]), _p(o["dL_dmeans3D"]), _p(o["dL_dopacity"]), _p(o["dL_dcolors"]),
+                  _p(o["dL_dsh"]), _p(o["dL_dscales"]), _p(o["dL_drots"]), _p(o["dL_dcov3D"]), st)
         torch.cuda.synchronize(dev)
         return {k: (None if v is None else v.cpu().numpy()) for k, v in o.items()}

@@ -159,7 +159,7 @@ def test_abi_of_round_4_still_steps():
     a.beta1, a.beta2, a.eps, a.weight_decay, a.n_groups = 0.9, 0.99, 1e-15, 0.01, 1
     a.lr[0], a.group[0], a.param[0] = 1e-2, 0, p.data_ptr()
     a.exp_avg, a.exp_avg_sq, a.step, a.pending_decay, a.found_inf, a.scratch = m.data_ptr(), v.data_ptr(), st.data_ptr(), None, None, scr.data_ptr()
-    _lib.check(_lib.lib().dm4d_adamw_message(C.byref(seg), C.byref(a), 1.0, torch.cuda.current_stream(dev).cuda_stream), "dm4d_adamw_message")
+    _lib.call("dm4d_adamw_message", C.byref(seg), C.byref(a), 1.0, torch.cuda.current_stream(dev).cuda_stream)
     torch.cuda.synchronize()
     assert float(st) == 1.0 and float((p - ref.detach()).abs().max()) <= 2e-6 * float(p.abs().max())
 
@@ -178,7 +178,6 @@ def test_slice_form_equals_the_whole_message_step():
     from dreammesh4d_amd.distributed import storage_flat
 
     dev = torch.device("cuda:0")
-    L = _lib.lib()
     st = torch.cuda.current_stream(dev).cuda_stream
     hyper = [(3.2e-3, 0.9, 0.999, 1e-15, 0.0), (3.2e-2, 0.8, 0.95, 1e-10, 0.03)]
 
@@ -228,7 +227,7 @@ def test_slice_form_equals_the_whole_message_step():
                         seg.index[k], a.param[k] = ix.data_ptr() + 8 * (s0 - o), base
                 a.exp_avg, a.exp_avg_sq = m.data_ptr() + 4 * lo, v.data_ptr() + 4 * lo
                 a.step, a.pending_decay, a.found_inf, a.scratch = steps[r].data_ptr(), None, flag.data_ptr(), scal.data_ptr()
-                _lib.check(L.dm4d_adamw_step(C.byref(seg), C.byref(a), 1.0, st), "dm4d_adamw_step")
+                _lib.call("dm4d_adamw_step", C.byref(seg), C.byref(a), 1.0, st)
             if it == 1:                                             # masked step: the send slices hold the CURRENT parameter values
                 cur = D.ShardedAdamW([{"params": params, "lr": 0.0}], red)
                 cur._pack_params()

@@ -144,9 +144,8 @@ def test_attention_writes_only_its_output_and_is_deterministic(B, L, H, D):
         out = buf[pad:pad + n]
         base = qkv.data_ptr()
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().dm4d_attention_f16(B, L, H, D, base, base + H * D * 2, base + 2 * H * D * 2, L * 3 * H * D, 3 * H * D,
-                                                     out.data_ptr(), float(D ** -0.5), torch.cuda.current_stream(dev).cuda_stream),
-                       "dm4d_attention_f16")
+            _lib.call("dm4d_attention_f16", B, L, H, D, base, base + H * D * 2, base + 2 * H * D * 2, L * 3 * H * D, 3 * H * D, out.data_ptr(),
+                      float(D ** -0.5), torch.cuda.current_stream(dev).cuda_stream)
         torch.cuda.synchronize()
         assert bool((buf[:pad] == 0x5A5A).all()) and bool((buf[pad + n:] == 0x5A5A).all()), "write outside out"
         outs.append(out.clone())

@@ -1,10 +1,16 @@
 """CPU-side checks of the C-ABI library: it loads without a GPU and exports every symbol
 include/dm4d.h declares (no compute calls here)."""
 import ctypes
+import os
+import re
+import subprocess
 
 import pytest
 
 from dreammesh4d_amd import _lib
+
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dm4d.h")
 
 
 def test_library_loads_and_exports_every_declared_symbol():
@@ -13,9 +19,85 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert len(declared) >= 15
     missing = [s for s in declared if not hasattr(L, s)]
     assert not missing, missing
-    # the ctypes signature table covers the same set
-    assert sorted(_lib._SIGNATURES) == declared
+    # the derived signatures have exactly the names the header declares (found here by a search of their own, not by the parser)
+    with open(HEADER) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    names = sorted(set(re.findall(r"\b(dm4d_[a-z0-9_]+)\s*\(", text)) - {"dm4d_alloc_fn"})
+    assert len(names) == 127 and sorted(_lib._SIGNATURES) == names == declared
+    # and each one is bound on the loaded library with the derived return type and number of arguments
+    for name, (res, args) in _lib._SIGNATURES.items():
+        fn = getattr(L, name)
+        assert callable(fn) and fn.restype is res and len(fn.argtypes) == len(args) and list(fn.argtypes) == args, name
     assert L.dm4d_version() >= 100
+
+
+def test_struct_layouts_equal_the_c_compilers(tmp_path):
+    """sizeof of every struct of include/dm4d.h, offsetof and size of every field: what the host C compiler says against the
+    ctypes classes derived from the header (field names taken from the classes)."""
+    assert len(_lib._STRUCTS) == 12
+    prog = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void) {']
+    for cname, cls in _lib._STRUCTS.items():
+        prog.append(f'    printf("{cname} %zu\\n", sizeof({cname}));')
+        for field, _ in cls._fields_:
+            prog.append(f'    printf("{cname}.{field} %zu %zu\\n", offsetof({cname}, {field}), sizeof((({cname} *)0)->{field}));')
+    prog += ['    return 0;', '}', '']
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(prog))
+    subprocess.run([os.environ.get("CC", "cc"), "-std=c99", "-o", str(exe), str(src)], check=True, capture_output=True, text=True)
+    got = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    want = {}
+    for cname, cls in _lib._STRUCTS.items():
+        want[cname] = str(ctypes.sizeof(cls))
+        for field, _ in cls._fields_:
+            want[f"{cname}.{field}"] = f"{getattr(cls, field).offset} {getattr(cls, field).size}"
+    assert len(want) == 12 + sum(len(c._fields_) for c in _lib._STRUCTS.values()) and got == want
+    assert ctypes.sizeof(_lib.StepDesc) == 1088 and _lib.StepDesc is _lib._STRUCTS["dm4d_step_desc"]
+
+
+def test_pinned_prototypes():
+    """Entry points that between them have every shape the header parser must get right, against signatures written out by hand
+    from include/dm4d.h."""
+    C = ctypes
+    P, vp, i32, i64, u32, f64, size = C.POINTER, C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_double, C.c_size_t
+    pinned = {
+        "dm4d_last_error": (C.c_char_p, []),
+        "dm4d_profile_enable": (None, [C.c_uint]),
+        "dm4d_profile_collect": (i64, [C.c_int, vp]),
+        "dm4d_device_arch": (C.c_int, [C.c_int, vp, C.c_int]),
+        "dm4d_rasterize_forward": (i64, [P(_lib.RasterSettings), P(_lib.RasterInputs), vp, vp, vp, vp, _lib.ALLOC_FN, vp, vp]),
+        "dm4d_rasterize_backward": (C.c_int, [P(_lib.RasterSettings), P(_lib.RasterInputs), vp, vp, vp, i64, vp, vp, i64,
+                                              vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dm4d_raster_read_image_state": (C.c_int, [vp, vp, vp, i32, i32, i32, i64, vp, vp, vp]),
+        "dm4d_cg_batched_f64": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, f64, i32, vp, vp]),
+        "dm4d_simplify_vertex_keys": (C.c_int, [i64, vp, f64, f64, f64, f64, i64, i64, i64, vp, vp]),
+        "dm4d_tex_accumulate": (C.c_int, [i32, vp, vp, i64, u32, vp, size, i32, vp, vp, vp]),
+        "dm4d_conv3x3_s2_dgrad_nhwc_f16": (C.c_int, [i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+        "dm4d_nodenet_backward": (C.c_int, [i32, i32, i32, vp, vp, i32, vp, vp, vp, P(_lib.MlpWeights), vp, vp, vp, vp, vp,
+                                            i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, P(_lib.MlpWeightsGrad), vp, vp]),
+        "dm4d_step_create": (C.c_int, [P(_lib.StepDesc), vp]),
+        "dm4d_step_destroy": (None, [vp]),
+        "dm4d_knn_points": (C.c_int, [i32, i32, i32, vp, vp, i32, i32, vp, size, vp, vp, vp]),
+    }
+    for name, want in pinned.items():
+        assert _lib._SIGNATURES[name] == want, name
+    assert len(_lib._SIGNATURES["dm4d_rasterize_backward"][1]) == 21
+
+
+def test_header_constants():
+    assert _lib.DM4D_GRAD_PYPOSE == 0x100 and _lib.DM4D_ERR_UNSUPPORTED == -4
+    assert _lib.DM4D_MAX_GRAD_SEGMENTS == _lib.MAX_GRAD_SEGMENTS == 64
+    assert _lib.DM4D_ABI_VERSION == _lib.abi_version() == 107
+
+
+@pytest.mark.parametrize("text, offending", [
+    ("typedef struct s { int32_t n; foo_t x; } s;", "foo_t x"),                       # a field of unknown type
+    ("#define DM4D_N 4\ntypedef struct s { float a[DM4D_N]; float b[DM4D_M]; } s;", "float b[DM4D_M]"),    # a bound that is no #define
+    ("int dm4d_f(int32_t n, const bar_t *x, void *stream);", "const bar_t *x"),       # an argument of unknown type
+])
+def test_header_parser_fails_loudly(text, offending):
+    with pytest.raises(ValueError) as e:
+        _lib.parse_header(text)
+    assert offending in str(e.value)
 
 
 def test_workspace_size_queries_are_monotone_and_aligned():

@@ -77,7 +77,6 @@ def test_distcuda2_one_million_points_box_search_bit_exact(kind):
     print(f"distCUDA2 {kind}: {n} points in {dt * 1e3:.1f} ms (box search)")
     sub = pts[:30_000]
     from dreammesh4d_amd import _lib
-    L = _lib.lib()
     ts, out = torch.tensor(sub, device="cuda:0"), torch.empty(len(sub), device="cuda:0")
-    _lib.check(L.dm4d_dist2_knn3(len(sub), ts.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream))     # exhaustive
+    _lib.call("dm4d_dist2_knn3", len(sub), ts.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)     # exhaustive
     assert np.array_equal(out.cpu().numpy().view(np.uint32), distCUDA2(ts).cpu().numpy().view(np.uint32))

@@ -235,6 +235,6 @@ def test_errors():
             assert rc == -1, (K, excl, n_pts, method)                       # DM4D_ERR_INVALID
             assert bool((d == -7.0).all()) and bool((i == -7).all())
     with pytest.raises(_lib.Dm4dError):
-        _lib.check(L.dm4d_knn_points(10, 40, 8, q.data_ptr(), p.data_ptr(), 0, 2, None, 0, d.data_ptr(), i.data_ptr(), st), "dm4d_knn_points")
+        _lib.call("dm4d_knn_points", 10, 40, 8, q.data_ptr(), p.data_ptr(), 0, 2, None, 0, d.data_ptr(), i.data_ptr(), st)
     rc = L.dm4d_knn_points(10, 40, 8, q.data_ptr(), p.data_ptr(), 0, 1, None, 0, d.data_ptr(), i.data_ptr(), st)
     assert rc == -3 and bool((i == -7).all())                                # DM4D_ERR_CAPACITY: no scratch given

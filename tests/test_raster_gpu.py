@@ -465,8 +465,8 @@ def test_one_shot_forward_with_alloc_callback():
     cb = _lib.ALLOC_FN(alloc)
     color, depth, alpha = torch.empty(3, cam.H, cam.W, device=dev), torch.empty(cam.H, cam.W, device=dev), torch.empty(cam.H, cam.W, device=dev)
     radii = torch.empty(h.N, dtype=torch.int32, device=dev)
-    D = _lib.check(L.dm4d_rasterize_forward(h.settings, h.inputs, color.data_ptr(), depth.data_ptr(), alpha.data_ptr(),
-                                            radii.data_ptr(), cb, None, st), "dm4d_rasterize_forward")
+    D = _lib.call("dm4d_rasterize_forward", h.settings, h.inputs, color.data_ptr(), depth.data_ptr(), alpha.data_ptr(), radii.data_ptr(), cb, None,
+                  st)
     torch.cuda.synchronize()
     assert D == o.D == h.D
     assert [w for w, _ in calls] == [0, 1, 2]                       # geom, then (after the one sync) binning and image

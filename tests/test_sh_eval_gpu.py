@@ -30,12 +30,11 @@ def _sh_forward(points, campos, sh, degree):
     """dm4d_sh_eval_forward -> (rgb, clamped) as device tensors."""
     from dreammesh4d_amd import _lib
 
-    L = _lib.lib()
     N, M = int(sh.shape[0]), int(sh.shape[1])
     rgb = torch.full((N, 3), float("nan"), device=_dev())
     cl = torch.full((N, 3), 7, dtype=torch.uint8, device=_dev())
-    _lib.check(L.dm4d_sh_eval_forward(N, degree, M, points.data_ptr(), campos.data_ptr(), sh.data_ptr(), rgb.data_ptr(), cl.data_ptr(),
-                                      torch.cuda.current_stream(_dev()).cuda_stream), "dm4d_sh_eval_forward")
+    _lib.call("dm4d_sh_eval_forward", N, degree, M, points.data_ptr(), campos.data_ptr(), sh.data_ptr(), rgb.data_ptr(), cl.data_ptr(),
+              torch.cuda.current_stream(_dev()).cuda_stream)
     torch.cuda.synchronize()
     return rgb, cl
 
@@ -43,13 +42,11 @@ def _sh_forward(points, campos, sh, degree):
 def _sh_backward(points, campos, sh, degree, clamped, g):
     from dreammesh4d_amd import _lib
 
-    L = _lib.lib()
     N, M = int(sh.shape[0]), int(sh.shape[1])
     dsh = torch.full((N, M, 3), float("nan"), device=_dev())
     dp = torch.full((N, 3), float("nan"), device=_dev())
-    _lib.check(L.dm4d_sh_eval_backward(N, degree, M, points.data_ptr(), campos.data_ptr(), sh.data_ptr(), clamped.data_ptr(),
-                                       g.data_ptr(), dsh.data_ptr(), dp.data_ptr(), torch.cuda.current_stream(_dev()).cuda_stream),
-               "dm4d_sh_eval_backward")
+    _lib.call("dm4d_sh_eval_backward", N, degree, M, points.data_ptr(), campos.data_ptr(), sh.data_ptr(), clamped.data_ptr(), g.data_ptr(),
+              dsh.data_ptr(), dp.data_ptr(), torch.cuda.current_stream(_dev()).cuda_stream)
     torch.cuda.synchronize()
     return dsh, dp
 

@@ -155,7 +155,6 @@ def test_glue_kernels_element_by_element_against_torch_autograd():
     from dreammesh4d_amd import _lib
 
     dev = torch.device("cuda:0")
-    Lb = _lib.lib()
     for B, clip in ((3, None), (4, 0.25), (1, None)):
         g = torch.Generator().manual_seed(10 + B)
         moments = torch.randn(B, 8, 32, 32, generator=g)
@@ -189,14 +188,13 @@ def test_glue_kernels_element_by_element_against_torch_autograd():
         x_in = torch.empty(2 * B, 8, 32, 32, device=dev, dtype=torch.float16).contiguous(memory_format=torch.channels_last)
         t2 = torch.empty(2 * B, dtype=torch.long, device=dev)
         s = torch.cuda.current_stream().cuda_stream
-        _lib.check(Lb.dm4d_sds_prepare(B, 32, 32, scale, ptr(md), st(md), ptr(post), st(post), ptr(noise), st(noise), ptr(lat2), st(lat2), ptr(t),
-                                       ptr(alphas), ptr(cc), st(cc), ptr(fidx), ptr(x_in), st(x_in), ptr(t2), s), "dm4d_sds_prepare")
+        _lib.call("dm4d_sds_prepare", B, 32, 32, scale, ptr(md), st(md), ptr(post), st(post), ptr(noise), st(noise), ptr(lat2), st(lat2), ptr(t),
+                  ptr(alphas), ptr(cc), st(cc), ptr(fidx), ptr(x_in), st(x_in), ptr(t2), s)
         dm = torch.empty(md.shape, device=dev, dtype=torch.float16)
         lo, gn = torch.empty((), device=dev), torch.empty((), device=dev)
         cl = None if clip is None else torch.tensor(clip, device=dev)
-        _lib.check(Lb.dm4d_sds_finish(B, 32, 32, scale, gs, ptr(pred), st(pred), ptr(lat2), st(lat2), ptr(noise), st(noise), ptr(t), ptr(alphas),
-                                      None if cl is None else ptr(cl), ptr(md), st(md), ptr(post), st(post), ptr(dm), st(dm), ptr(lo), ptr(gn), s),
-                   "dm4d_sds_finish")
+        _lib.call("dm4d_sds_finish", B, 32, 32, scale, gs, ptr(pred), st(pred), ptr(lat2), st(lat2), ptr(noise), st(noise), ptr(t), ptr(alphas),
+                  None if cl is None else ptr(cl), ptr(md), st(md), ptr(post), st(post), ptr(dm), st(dm), ptr(lo), ptr(gn), s)
         assert torch.equal(latents.detach(), lat2)
         assert torch.equal(x_in[:B, :4], noisy.half()) and torch.equal(x_in[B:, :4], noisy.half())
         assert torch.equal(x_in[:B, 4:], torch.zeros_like(x_in[:B, 4:])) and torch.equal(x_in[B:, 4:], cc[fidx])

@@ -9,7 +9,6 @@ wl = bench.Workload(dev, 0, 1, views_per_frame=2)
 for _ in range(3):
     wl.step()
 torch.cuda.synchronize()
-L = _lib.lib()
 B, blocks = 1, 8 * 4096 + 8 * 256      # backward: 8 x 256 wide blocks first, then the quadrants
 buf = torch.zeros(B * blocks, 4, dtype=torch.int64, device=dev)
 
@@ -44,7 +43,7 @@ def analyse(name, a):
     print("   top work:", [(int(work[i]), round(float((t0[i]-base)/100.0),1), round(float(dur[i]),1)) for i in idx])
 
 MINW = int(sys.argv[1]) if len(sys.argv) > 1 else 0
-_lib.check(L.dm4d_debug_trace(buf.data_ptr(), MINW))
+_lib.call("dm4d_debug_trace", buf.data_ptr(), MINW)
 # forward only
 out = wl.step.__func__  # noqa
 dx, dr, ds, do = wl.net.node_outputs(wl.nodes, wl.frame_t)
@@ -55,7 +54,7 @@ buf.zero_()
 torch.autograd.backward([o["color"], o["alpha"]], [wl.gC, wl.gA])
 torch.cuda.synchronize()
 bw = buf.cpu().numpy().copy()
-_lib.check(L.dm4d_debug_trace(None, 0))
+_lib.call("dm4d_debug_trace", None, 0)
 analyse("render_fwd", fw[:8 * 4096])
 analyse("render_bwd (wide blocks: one wave per long cell)", bw[:8 * 256])
 analyse("render_bwd (regular blocks)", bw[8 * 256:])
