@@ -297,7 +297,8 @@ class DeformationNetwork(nn.Module):
         dx [B,M,3], dr [B,M,4], ds [B,M,6] | None, do [B,M] | None  (dynamic_sugar.py:420-431, ts*2-1).
 
         On a HIP device the 24 grid_sample calls are ONE fused kernel (csrc/hexplane.hip) with an
-        atomic-free gather backward; the plan (static gather lists) is built once per node set."""
+        atomic-free gather backward; the plan (gather lists) is built once per node set and again when the nodes move
+        (`build_plan`)."""
         B, M = int(timestamps.shape[0]), int(nodes.shape[0])
         if nodes.is_cuda:
             from . import hexplane as hx
@@ -350,16 +351,24 @@ class DeformationNetwork(nn.Module):
         do = None if do is None else do.view(B, M)
         return r(dx, 3), r(dr, 4), r(ds, 6), do
 
-    def build_plan(self, nodes):
-        """The static gather lists of the fused HexPlane backward for this node set (built once; the nodes never move).
-        Training loops call it in their constructor so that everything derived from the plan -- the structured-sparse
-        gradient message, the sharded optimiser's state -- exists before the first step."""
+    def build_plan(self, nodes, force=False):
+        """The gather lists of the fused HexPlane backward for this node set, built once and reused while the nodes stay where
+        they are.  Training loops call it in their constructor so that everything derived from the plan -- the structured-sparse
+        gradient message, the sharded optimiser's state -- exists before the first step.
+
+        The plan belongs to node POSITIONS (hexplane.HexPlan keeps its own copy of them).  The cached one is reused while the
+        key of `nodes` -- storage address, version counter, length, device, dtype, strides -- is unchanged: an in-place write
+        (`nodes.copy_(...)`, an optimiser step) bumps the version counter, and the next call builds a new plan, whose persistent
+        gradient planes (`grads_in_place`) start from zero.  The tensor the plan was built from stays referenced, so that its
+        address cannot pass to another tensor meanwhile.  Not seen: writes through `nodes.data`, which bypass the version
+        counter -- pass force=True after one.  The check costs a handful of attribute reads per step."""
         from . import hexplane as hx
 
-        key = (nodes.data_ptr(), int(nodes.shape[0]), nodes.device)
-        if getattr(self, "_hex_plan_key", None) != key:
+        key = (nodes.data_ptr(), nodes._version, int(nodes.shape[0]), nodes.device, nodes.dtype, nodes.stride())
+        if force or getattr(self, "_hex_plan_key", None) != key:
             self._hex_plan = hx.HexPlan(self.deformation_net.grid, nodes)
             self._hex_plan_key = key
+            self._hex_plan_source = nodes.detach()       # keeps the storage, and so the address in the key, alive
         return self._hex_plan
 
     def get_mlp_parameters(self):

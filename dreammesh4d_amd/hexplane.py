@@ -18,7 +18,13 @@ TIME = (2, 4, 5)
 
 
 class HexPlan:
-    """Static gather lists of the backward for one node set (the nodes never move)."""
+    """Gather lists of the backward for one node set AT ITS POSITIONS of the moment of construction.
+
+    `self.nodes` is the plan's own float32 copy of them, never an alias of the caller's tensor: the forward, the backward's
+    weights and the texel / column lists all read this copy, so one plan is always consistent with itself, whatever happens
+    to the caller's tensor afterwards.  Nodes that move need a new plan -- `DeformationNetwork.build_plan` notices in-place
+    writes by the tensor's version counter and builds one; the old plan's `grad_buffers` (touched texels of the OLD positions)
+    go with it."""
 
     def __init__(self, field, nodes):
         dev = nodes.device
@@ -33,7 +39,7 @@ class HexPlan:
         self.res_c = self.res.ctypes.data_as(C.c_void_p)
         self.aabb = field.aabb.detach().cpu().numpy().astype(np.float32).reshape(6).copy()
         self.aabb_c = self.aabb.ctypes.data_as(C.c_void_p)
-        self.nodes = nodes.detach().to(torch.float32).contiguous()
+        self.nodes = nodes.detach().to(torch.float32, copy=True).contiguous()
         i0 = torch.empty(self.S, 3, self.M, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
             _lib.call("dm4d_hexplane_axis_index", self.S, self.M, self.res_c, self.aabb_c, _p(self.nodes), _p(i0), _lib.stream(dev))

@@ -18,7 +18,11 @@ def _need_gpu():
 @pytest.mark.parametrize("layout", ["channels_last", "contiguous"])
 def test_fused_hexplane_matches_grid_sample_path(resolution, multires, M, B, heads, layout):
     """Both plane storages the C ABI accepts: the module's own (torch.channels_last) and the reference's contiguous
-    [1,32,H,W] tensors."""
+    [1,32,H,W] tensors.
+
+    The (1, 2, 4) case has in_dim = 96: no multiple of 64, so `node_outputs` runs the HexPlane kernels in front of the MLP as
+    torch ops -- it covers that combination and never reaches csrc/deform_mlp.hip or csrc/nodenet.hip.  The fused MLP at every
+    width it takes (64, 128, 192, 256) is compared in tests/test_node_network_edges_gpu.py."""
     _need_gpu()
     from dreammesh4d_amd.deformation import DeformationNetwork
 
