@@ -132,9 +132,11 @@ class ARAPCoach:
         pos = {(a, b): k for k, (a, b) in enumerate(zip(src.tolist(), nbr.tolist()))}
         rev = np.asarray([pos[(b, a)] for a, b in zip(src.tolist(), nbr.tolist())], np.int64)
         e = (verts_c[src] - verts_c[nbr]).numpy()
-        T = lambda a, dt: torch.as_tensor(a, dtype=dt, device=self.device).contiguous()
-        self._off, self._nbr, self._rev = T(off, torch.int32), T(nbr, torch.int32), T(rev, torch.int32)
-        self._w, self._e = T(w, torch.float32), T(e, torch.float32)
+        # a mesh without edges (isolated vertices only): one unused entry, an empty tensor's null pointer is refused by the library
+        pad = lambda a: a if len(a) else np.zeros((1,) + a.shape[1:], a.dtype)
+        on_dev = lambda a, dt: torch.as_tensor(pad(a), dtype=dt, device=self.device).contiguous()
+        self._off, self._nbr, self._rev = on_dev(off, torch.int32), on_dev(nbr, torch.int32), on_dev(rev, torch.int32)
+        self._w, self._e = on_dev(w, torch.float32), on_dev(e, torch.float32)
         self.edge_weights, self.edge_sources, self.edge_targets = w, src, nbr
 
     def _init_knn(self, verts):
