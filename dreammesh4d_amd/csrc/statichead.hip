@@ -15,6 +15,8 @@
 //             by the caller in a fixed order; the half-size images of the random views;
 //   backward: one pass that WRITES dL/dcolor [B,6,H,W], dL/ddepth, dL/dalpha [B,1,H,W]: a pixel recomputes the three quantities at
 //             its four neighbours (the total variation's gradient is a five-point stencil of them) instead of reading them back.
+// Checked against the torch composition (tests/test_static_stage_gpu.py) and, element by element at every branch point, against a
+// float64 closed form (tests/test_static_kernels_edges_gpu.py; cases, reference and bounds: tests/static_kernels_edges.py).
 #include "common.h"
 #include "../../include/dm4d.h"
 
@@ -193,7 +195,7 @@ __global__ __launch_bounds__(kSHThreads) void k_static_head_bwd(SHeadArgs a, con
                 d_alpha += dq[4 + k] * (nh[k] * 0.5f);
                 dotp += nh[k] * gn[k];
             }
-            if (nrm > 1e-12f) {
+            if (nrm >= 1e-12f) {                        // (clamp_min passes the gradient at nrm == eps)
 #pragma unroll
                 for (int k = 0; k < 3; ++k) gv[k] = (gn[k] - nh[k] * dotp) / len;
             } else {                                    // (the clamp of the norm is active: x / eps)

@@ -12,7 +12,9 @@
 // forward: a thread per Gaussian; outputs are the rasterizer's inputs (means [N,3], rotations [N,4] (w,x,y,z), scales [N,3], opacities
 // [N], colors [N,6] = rgb | normal).  backward: a thread per FACE walks its G Gaussians, keeps the face's vertex gradients in registers
 // and adds them to dL/dpoints with 9 float atomics (the torch composition's index_add does the same); the per-Gaussian parameter
-// gradients are plain stores.  Checked against the torch composition and its autograd (tests/test_static_stage_gpu.py).
+// gradients are plain stores.  Checked against the torch composition and its autograd (tests/test_static_stage_gpu.py) and, element by
+// element at every branch point, against a float64 closed form (tests/test_static_kernels_edges_gpu.py; cases, reference and bounds:
+// tests/static_kernels_edges.py).
 #include "common.h"
 #include "../../include/dm4d.h"
 
@@ -26,17 +28,19 @@ __device__ __forceinline__ SA3 operator*(float s, SA3 a) { return SA3{s * a.x, s
 __device__ __forceinline__ float sdot(SA3 a, SA3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ SA3 scross(SA3 a, SA3 b) { return SA3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ SA3 sload(const float *p, int i) { return SA3{p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]}; }
-// F.normalize: x / max(|x|, 1e-12); its backward: (g - xhat (xhat . g)) / |x| where the clamp is inactive, g / eps where it is
-__device__ __forceinline__ SA3 snormalize(SA3 v, float &len) { len = fmaxf(sqrtf(sdot(v, v)), 1e-12f); return (1.0f / len) * v; }
-__device__ __forceinline__ SA3 snormalize_bwd(SA3 vhat, float len, SA3 g)
+// F.normalize: x / |x|.clamp_min(1e-12); its backward: (g - xhat (xhat . g)) / |x| where |x| >= eps (clamp_min passes the gradient
+// AT equality), g / eps below.  `norm` is the unclamped |x|.
+__device__ __forceinline__ SA3 snormalize(SA3 v, float &norm) { norm = sqrtf(sdot(v, v)); return (1.0f / fmaxf(norm, 1e-12f)) * v; }
+__device__ __forceinline__ SA3 snormalize_bwd(SA3 vhat, float norm, SA3 g)
 {
-    if (len <= 1e-12f) return (1.0f / len) * g;
+    const float len = fmaxf(norm, 1e-12f);
+    if (norm < 1e-12f) return (1.0f / len) * g;
     return (1.0f / len) * (g - sdot(vhat, g) * vhat);
 }
 
 constexpr float kSHC0 = 0.28209479177387814f;
 
-struct FaceFrame { SA3 v0, v1, v2, e1, e2, cr, n, d01, b1, cb, b2; float ln, l1, l2; };
+struct FaceFrame { SA3 v0, v1, v2, e1, e2, cr, n, d01, b1, cb, b2; float ln, l1, l2; /* unclamped norms of cr, d01, cb */ };
 __device__ __forceinline__ FaceFrame face_frame(const float *points, const int64_t *faces, int f)
 {
     FaceFrame F;
@@ -53,7 +57,7 @@ __device__ __forceinline__ FaceFrame face_frame(const float *points, const int64
 }
 
 // pytorch3d.transforms.matrix_to_quaternion on R = [n | r1 | r2] (columns), standardised to w >= 0, then F.normalize
-struct QuatFwd { float q[4]; float raw[4]; float x[4], qa[4]; int best; float den, sign, qlen; };
+struct QuatFwd { float q[4]; float raw[4]; float x[4], qa[4]; int best; float den, sign, qnorm, qlen; };
 __device__ __forceinline__ QuatFwd quat_from_columns(SA3 n, SA3 r1, SA3 r2)
 {
     // m[row][col]: col 0 = n, col 1 = r1, col 2 = r2
@@ -76,7 +80,8 @@ __device__ __forceinline__ QuatFwd quat_from_columns(SA3 n, SA3 r1, SA3 r2)
     float s2 = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) { o.raw[k] *= o.sign; s2 += o.raw[k] * o.raw[k]; }
-    o.qlen = fmaxf(sqrtf(s2), 1e-12f);
+    o.qnorm = sqrtf(s2);
+    o.qlen = fmaxf(o.qnorm, 1e-12f);
 #pragma unroll
     for (int k = 0; k < 4; ++k) o.q[k] = o.raw[k] / o.qlen;
     return o;
@@ -176,7 +181,7 @@ __global__ __launch_bounds__(128) void k_sugar_attr_bwd(SAArgs a, const float *_
             for (int k = 0; k < 4; ++k) { go[k] = g_rots[4 * i + k]; dotq += q.q[k] * go[k]; }
             float graw[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) graw[k] = (q.qlen <= 1e-12f ? go[k] / q.qlen : (go[k] - q.q[k] * dotq) / q.qlen) * q.sign;
+            for (int k = 0; k < 4; ++k) graw[k] = (q.qnorm < 1e-12f ? go[k] / q.qlen : (go[k] - q.q[k] * dotq) / q.qlen) * q.sign;
             // raw_k (before the sign) = c_k / den:  g c_k = graw_k / den;  g den = - sum graw_k c_k / den^2
             float gcand[4], gden = 0.f;
 #pragma unroll
@@ -207,7 +212,7 @@ __global__ __launch_bounds__(128) void k_sugar_attr_bwd(SAArgs a, const float *_
         if (g_cx) {
             // c = normalize(cx)
             float gx0, gx1;
-            if (cn <= 1e-12f) { gx0 = gc0 / cl; gx1 = gc1 / cl; }
+            if (cn < 1e-12f) { gx0 = gc0 / cl; gx1 = gc1 / cl; }           // (clamp_min passes the gradient at cn == eps)
             else { const float d = c0 * gc0 + c1 * gc1; gx0 = (gc0 - c0 * d) / cl; gx1 = (gc1 - c1 * d) / cl; }
             g_cx[2 * i] = gx0; g_cx[2 * i + 1] = gx1;
         }

@@ -6,7 +6,8 @@ masked depth; on the reference views the two masked MSEs; on the random views th
 terms -- is ~130 torch operators over 5 x 512^2 images forward + backward (1.3 ms of a 13.9 ms iteration).  ``static_head`` returns
 (terms [5] = mse_rgb, mse_mask, tv_rgb, tv_depth, tv_normal; half_rgb [n_rnd, H/2, W/2, 3]) with one launch each way; the torch
 composition it replaces stays in ``static_stage.StaticStage.iteration`` (CPU tensors, other renderers) and is what
-``tests/test_static_stage_gpu.py`` checks it against."""
+``tests/test_static_stage_gpu.py`` checks it against; ``tests/test_static_kernels_edges_gpu.py`` checks the kernels element by element
+at their branch points against a float64 closed form (``tests/static_kernels_edges.py``)."""
 import torch
 
 from . import _lib
