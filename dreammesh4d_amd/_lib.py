@@ -1,4 +1,4 @@
-"""ctypes binding of libdm4d_hip.so (C ABI: include/dm4d.h).
+"""ctypes binding of libdm4d_hip.so (C ABI: include/dm4d.h, and include/dm4d_isosurface.h for the mesh-extraction entry points).
 
 The product path has NO fallback: if the HIP library is missing or fails to load,
 importing an operator raises.  (The CPU restatements under oracle/ are test
@@ -120,6 +120,12 @@ MlpWeights, MlpWeightsGrad = _STRUCTS["dm4d_mlp_weights"], _STRUCTS["dm4d_mlp_we
 StepDesc = _STRUCTS["dm4d_step_desc"]
 GradSegments, AdamwArgs, AdamwStepArgs = _STRUCTS["dm4d_grad_segments"], _STRUCTS["dm4d_adamw_args"], _STRUCTS["dm4d_adamw_step_args"]
 
+# the mesh-extraction entry points have a header and a version of their own: include/dm4d.h keeps its functions and its number
+with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d_isosurface.h")) as _f:
+    _ISO_CONSTANTS, _ISO_STRUCTS, _ISO_SIGNATURES = parse_header(_f.read())
+ISO_RECORD_FLOATS = _ISO_CONSTANTS["DM4D_ISO_RECORD_FLOATS"]
+ISO_MAX_RESOLUTION = _ISO_CONSTANTS["DM4D_ISO_MAX_RESOLUTION"]
+
 
 def declared_symbols():
     """Every function include/dm4d.h declares."""
@@ -129,6 +135,16 @@ def declared_symbols():
 def abi_version() -> int:
     """DM4D_ABI_VERSION of include/dm4d.h (the header the binding is derived from)."""
     return _CONSTANTS["DM4D_ABI_VERSION"]
+
+
+def iso_declared_symbols():
+    """Every function include/dm4d_isosurface.h declares."""
+    return sorted(_ISO_SIGNATURES)
+
+
+def iso_abi_version() -> int:
+    """DM4D_ISO_ABI_VERSION of include/dm4d_isosurface.h."""
+    return _ISO_CONSTANTS["DM4D_ISO_ABI_VERSION"]
 
 
 def build(force: bool = False) -> str:
@@ -149,7 +165,7 @@ def lib() -> C.CDLL:
                 f"{SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  dreammesh4d_amd has no CPU fallback.")
         L = C.CDLL(SO_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_ISO_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -157,6 +173,9 @@ def lib() -> C.CDLL:
         if L.dm4d_version() != want:
             raise ImportError(f"{SO_PATH} has ABI version {L.dm4d_version()}, include/dm4d.h declares {want}: rebuild it "
                               "(`python -c 'import __graft_entry__ as g; g.build()'`)")
+        if L.dm4d_iso_version() != iso_abi_version():
+            raise ImportError(f"{SO_PATH} has isosurface ABI version {L.dm4d_iso_version()}, include/dm4d_isosurface.h declares "
+                              f"{iso_abi_version()}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
         _LIB = L
     return _LIB
 

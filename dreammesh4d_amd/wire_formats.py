@@ -8,6 +8,10 @@
   the reader follows the PLY format itself (ascii / binary_little_endian / binary_big_endian, any scalar property
   types, list-typed faces) and the writer emits the layout open3d uses (double positions and normals, uchar colours,
   ``list uchar uint vertex_indices``); byte-for-byte agreement with open3d's files is unpinned.
+* The Gaussians of a 3D Gaussian splatting run (``GaussianIO.save_ply`` / ``load_ply``,
+  custom/threestudio-dreammesh4d/geometry/gaussian_io.py:36-172, written there through plyfile): one ``vertex`` element of float
+  columns ``x y z nx ny nz f_dc_* f_rest_* opacity scale_* rot_*`` holding the pre-activation values --
+  ``read_gaussian_ply`` / ``write_gaussian_ply``, the input of ``python -m dreammesh4d_amd.isosurface``.
 * The Lightning checkpoint of a stage (``system.weights``): ``{"state_dict", "epoch", "global_step"}`` with the
   geometry's entries under ``geometry.`` -- ``load_module_weights`` of threestudio/utils/misc.py:33-63.
   ``DynamicSuGaR`` keeps the reference's parameter names, so the geometry entries load by name.
@@ -185,6 +189,89 @@ def read_mesh(path):
     if ext == "obj":
         return read_obj_geometry(path)
     raise ValueError(f"{path}: only .ply and .obj meshes are read")
+
+
+SH_C0 = 0.28209479177387814            # gaussian_base.py:32: SH2RGB(sh) = sh * C0 + 0.5
+
+
+def _numbered(names, prefix):
+    """The columns ``{prefix}{i}`` among `names`, by ascending i (load_ply sorts them the same way)."""
+    return sorted((n for n in names if n.startswith(prefix) and n[len(prefix):].isdigit()), key=lambda n: int(n[len(prefix):]))
+
+
+def write_gaussian_ply(path, xyz, f_dc, f_rest, opacity, scale, rot):
+    """Binary little-endian PLY in the column layout of ``GaussianIO.save_ply``: float ``x y z nx ny nz`` (normals zero),
+    ``f_dc_0..`` ([N,3]: the file's column order, the reference's ``_features_dc.transpose(1, 2).flatten(1)``), ``f_rest_0..``
+    ([N,K], K may be 0), ``opacity`` ([N] or [N,1]), ``scale_0..2`` ([N,3]), ``rot_0..3`` ([N,4]; w, x, y, z).  Every value is
+    stored as given: PRE-activation (logit opacity, log scales, raw quaternions)."""
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    n = len(xyz)
+    cols = [xyz, np.zeros((n, 3), np.float32), np.asarray(f_dc, np.float32).reshape(n, -1), np.asarray(f_rest, np.float32).reshape(n, -1),
+            np.asarray(opacity, np.float32).reshape(n, 1), np.asarray(scale, np.float32).reshape(n, -1), np.asarray(rot, np.float32).reshape(n, -1)]
+    names = ["x", "y", "z", "nx", "ny", "nz"] + [f"f_dc_{i}" for i in range(cols[2].shape[1])] + [f"f_rest_{i}" for i in range(cols[3].shape[1])] \
+        + ["opacity"] + [f"scale_{i}" for i in range(cols[5].shape[1])] + [f"rot_{i}" for i in range(cols[6].shape[1])]
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {n}"] + [f"property float {c}" for c in names] + ["end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode("ascii"))
+        fh.write(np.ascontiguousarray(np.concatenate(cols, axis=1), "<f4").tobytes())
+
+
+def read_gaussian_ply(path):
+    """The Gaussians of a file in ``GaussianIO.save_ply``'s layout (binary or ascii, scalar vertex columns of any type), float32:
+    the stored columns ``xyz`` [N,3], ``f_dc`` [N,3], ``f_rest`` [N,K], ``opacity_raw`` [N], ``scale_raw`` [N,3], ``rotation`` [N,4]
+    (raw; its users normalise it), and what the reference's activations make of them: ``opacity`` = sigmoid(opacity_raw) [N],
+    ``scaling`` = exp(scale_raw) [N,3], ``rgb`` = SH2RGB(f_dc) = f_dc * C0 + 0.5 [N,3]."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.index(b"\n", data.index(b"end_header")) + 1
+    header = data[:end].decode("ascii", "replace").splitlines()
+    if not header or header[0].strip() != "ply":
+        raise ValueError(f"{path}: not a PLY file")
+    fmt, count, props, in_vertex, seen = None, None, [], False, 0
+    for line in header[1:]:
+        tok = line.split()
+        if not tok:
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            seen += 1
+            in_vertex = tok[1] == "vertex"
+            if in_vertex:
+                if seen != 1:
+                    raise ValueError(f"{path}: the vertex element must come first")
+                count = int(tok[2])
+        elif tok[0] == "property" and in_vertex:
+            if tok[1] == "list":
+                raise ValueError(f"{path}: list property in the vertex element")
+            props.append((tok[2], _PLY_TYPES[tok[1]]))
+    if count is None:
+        raise ValueError(f"{path}: no vertex element")
+    if fmt == "ascii":
+        table = np.array(data[end:].split()[:count * len(props)], np.float64).reshape(count, len(props))
+        col = {name: table[:, i].astype(np.float32) for i, (name, _) in enumerate(props)}
+    elif fmt in ("binary_little_endian", "binary_big_endian"):
+        bo = "<" if fmt == "binary_little_endian" else ">"
+        arr = np.frombuffer(data, np.dtype([(name, bo + t) for name, t in props]), count, end)
+        col = {name: arr[name].astype(np.float32) for name, _ in props}
+    else:
+        raise ValueError(f"{path}: unsupported PLY format {fmt!r}")
+    names = [name for name, _ in props]
+    groups = {"xyz": ["x", "y", "z"], "f_dc": _numbered(names, "f_dc_"), "f_rest": _numbered(names, "f_rest_"),
+              "scale_raw": _numbered(names, "scale_"), "rotation": _numbered(names, "rot_")}
+    want = {"xyz": 3, "f_dc": 3, "scale_raw": 3, "rotation": 4}
+    for key, k in want.items():
+        if len(groups[key]) != k or any(c not in col for c in groups[key]):
+            raise ValueError(f"{path}: expected {k} columns for {key}, found {groups[key]}")
+    if "opacity" not in col:
+        raise ValueError(f"{path}: no opacity column")
+    out = {key: np.stack([col[c] for c in cs], 1) if cs else np.zeros((count, 0), np.float32) for key, cs in groups.items()}
+    out["opacity_raw"] = col["opacity"]
+    one = np.float32(1.0)
+    out["opacity"] = one / (one + np.exp(-out["opacity_raw"]))
+    out["scaling"] = np.exp(out["scale_raw"])
+    out["rgb"] = out["f_dc"] * np.float32(SH_C0) + np.float32(0.5)
+    return out
 
 
 def vertex_normals(verts, faces):
