@@ -20,6 +20,8 @@
 namespace dm4d {
 
 constexpr int kGeoMaxK = 16;
+// a ranks strictly before b in numpy's sort order: NaN last (after +inf), NaN beside NaN a tie
+__device__ __forceinline__ bool geo_ranks_before(float a, float b) { return a < b || (b != b && a == a); }
 
 __global__ __launch_bounds__(256) void k_geo_init(int V, int M, const int32_t *__restrict__ src, float *__restrict__ d)
 {
@@ -50,15 +52,15 @@ __global__ __launch_bounds__(256) void k_geo_select(int V, int M, int K, const f
 {
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v >= V) return;
+    // (as k_graph_select of heat.hip: the first K + 1 nodes always enter, so no index outside [0, M) can be written)
     float bd[kGeoMaxK + 1];
     int bi[kGeoMaxK + 1];
     const int K1 = K + 1;
-    for (int k = 0; k < K1; ++k) { bd[k] = 3.4e38f; bi[k] = -1; }
     for (int m = 0; m < M; ++m) {
         const float dm = d[(size_t)m * V + v];
-        if (dm < bd[K1 - 1]) {                       // strict: an equal distance keeps the earlier (lower) index ahead
-            int k = K1 - 1;
-            while (k > 0 && dm < bd[k - 1]) { bd[k] = bd[k - 1]; bi[k] = bi[k - 1]; --k; }
+        if (m < K1 || geo_ranks_before(dm, bd[K1 - 1])) {                   // strict: an equal distance keeps the earlier (lower) index ahead
+            int k = m < K1 ? m : K1 - 1;
+            while (k > 0 && geo_ranks_before(dm, bd[k - 1])) { bd[k] = bd[k - 1]; bi[k] = bi[k - 1]; --k; }
             bd[k] = dm;
             bi[k] = m;
         }
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(256) void k_geo_select(int V, int M, int K, const f
     const float px = verts[3 * (size_t)v], py = verts[3 * (size_t)v + 1], pz = verts[3 * (size_t)v + 2];
     float e[kGeoMaxK + 1];
     for (int k = 0; k < K1; ++k) {
-        const int m = bi[k] < 0 ? 0 : bi[k];
+        const int m = bi[k];
         const float dx = px - node_xyz[3 * (size_t)m], dy = py - node_xyz[3 * (size_t)m + 1], dz = pz - node_xyz[3 * (size_t)m + 2];
         e[k] = sqrtf((dx * dx + dy * dy) + dz * dz);
     }
@@ -76,9 +78,12 @@ __global__ __launch_bounds__(256) void k_geo_select(int V, int M, int K, const f
         w[k] = t * t;
         sum += w[k];
     }
+    // all K + 1 nodes equidistant or on the vertex: the uniform row where the reference's formula gives NaN
+    const bool ok = e[K] > 0.f && sum > 0.f && sum <= 3.4028234e38f;
+    const float uniform = 1.0f / (float)K;
     for (int k = 0; k < K; ++k) {
         idx[(size_t)v * K + k] = bi[k];
-        weights[(size_t)v * K + k] = w[k] / sum;
+        weights[(size_t)v * K + k] = ok ? w[k] / sum : uniform;
     }
 }
 

@@ -147,7 +147,8 @@ __global__ __launch_bounds__(256) void k_cg_roll(int S, double *__restrict__ rz,
     double rel = 0.0;
     if (s < S) {
         rz[s] = rz_new[s];
-        rel = bb[s] > 0.0 ? rr[s] / bb[s] : 0.0;
+        rel = bb[s] > 0.0 ? rr[s] / bb[s] : (bb[s] == 0.0 ? 0.0 : rr[s] + bb[s]);      // (a NaN in b must not read as "converged")
+        if (!(rel == rel)) rel = HUGE_VAL;            // fmax drops a NaN: carry it to the host as +inf
     }
     // max over the workgroup -> one double per workgroup (the host takes the max of a handful of values)
     __shared__ double s_m[256];
@@ -170,14 +171,22 @@ __global__ __launch_bounds__(256) void k_heat_face_dirs(int F, int S, const int3
     if (s >= S || f >= F) return;
     const double u0 = U[(size_t)faces[3 * f] * S + s], u1 = U[(size_t)faces[3 * f + 1] * S + s], u2 = U[(size_t)faces[3 * f + 2] * S + s];
     const double *g = G + (size_t)f * 9;
-    const double gx = (u0 * g[0] + u1 * g[3]) + u2 * g[6], gy = (u0 * g[1] + u1 * g[4]) + u2 * g[7], gz = (u0 * g[2] + u1 * g[5]) + u2 * g[8];
-    const double n = fmax(sqrt((gx * gx + gy * gy) + gz * gz), 1e-300);
+    double gx = (u0 * g[0] + u1 * g[3]) + u2 * g[6], gy = (u0 * g[1] + u1 * g[4]) + u2 * g[7], gz = (u0 * g[2] + u1 * g[5]) + u2 * g[8];
+    // The far field of a heat solution underflows when squared (|grad u| < 1e-154).  Scaling by a power of two is exact: the same
+    // bits as without it wherever the squares neither underflow nor overflow, and a unit vector everywhere else.
+    const double big = fmax(fmax(fabs(gx), fabs(gy)), fabs(gz));
+    int ex = 0;
+    if (big > 0.0) frexp(big, &ex);
+    gx = ldexp(gx, -ex); gy = ldexp(gy, -ex); gz = ldexp(gz, -ex);
+    const double n = fmax(sqrt((gx * gx + gy * gy) + gz * gz), 1e-300);        // (the floor: only an exactly zero gradient now)
     XT[((size_t)3 * f + 0) * S + s] = -gx / n;
     XT[((size_t)3 * f + 1) * S + s] = -gy / n;
     XT[((size_t)3 * f + 2) * S + s] = -gz / n;
 }
 
 constexpr int kSelMaxK = 16;
+// a ranks strictly before b in numpy's sort order: NaN last (after +inf), NaN beside NaN a tie
+__device__ __forceinline__ bool ranks_before(double a, double b) { return a < b || (b != b && a == a); }
 // score[m][s] (row stride ld): for source vertex v0 + s the K + 1 nodes of smallest score, ties towards the lower node index;
 // weights (1 - e_k / e_K)^2 with Euclidean distances to the node positions, row-normalised (dynamic_sugar.py:842-861)
 __global__ __launch_bounds__(256) void k_graph_select(int S, int M, int K, const double *__restrict__ score, int ld, int v0,
@@ -186,15 +195,17 @@ __global__ __launch_bounds__(256) void k_graph_select(int S, int M, int K, const
 {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= S) return;
+    // Insertion into the sorted list of the K + 1 best so far.  The first K + 1 nodes always enter (no sentinel that a large score
+    // could fail to beat: every index written lies in [0, M)), a later one where it ranks strictly before the last kept.  The
+    // order is numpy's: NaN after everything, +inf included; equal scores keep the lower node index ahead.
     double bd[kSelMaxK + 1];
     int bi[kSelMaxK + 1];
     const int K1 = K + 1;
-    for (int k = 0; k < K1; ++k) { bd[k] = 1.0e300; bi[k] = -1; }
     for (int m = 0; m < M; ++m) {
         const double dm = score[(size_t)m * ld + s];
-        if (dm < bd[K1 - 1]) {
-            int k = K1 - 1;
-            while (k > 0 && dm < bd[k - 1]) { bd[k] = bd[k - 1]; bi[k] = bi[k - 1]; --k; }
+        if (m < K1 || ranks_before(dm, bd[K1 - 1])) {
+            int k = m < K1 ? m : K1 - 1;
+            while (k > 0 && ranks_before(dm, bd[k - 1])) { bd[k] = bd[k - 1]; bi[k] = bi[k - 1]; --k; }
             bd[k] = dm;
             bi[k] = m;
         }
@@ -203,7 +214,7 @@ __global__ __launch_bounds__(256) void k_graph_select(int S, int M, int K, const
     const float px = verts[3 * v], py = verts[3 * v + 1], pz = verts[3 * v + 2];
     float e[kSelMaxK + 1];
     for (int k = 0; k < K1; ++k) {
-        const int m = bi[k] < 0 ? 0 : bi[k];
+        const int m = bi[k];
         const float dx = px - node_xyz[3 * (size_t)m], dy = py - node_xyz[3 * (size_t)m + 1], dz = pz - node_xyz[3 * (size_t)m + 2];
         e[k] = sqrtf((dx * dx + dy * dy) + dz * dz);
     }
@@ -213,9 +224,13 @@ __global__ __launch_bounds__(256) void k_graph_select(int S, int M, int K, const
         w[k] = t * t;
         sum += w[k];
     }
+    // all K + 1 nodes equidistant (sum == 0) or on the vertex (e[K] == 0: 0 / 0 or an infinite ratio): the uniform row, where the
+    // reference's formula gives NaN
+    const bool ok = e[K] > 0.f && sum > 0.f && sum <= 3.4028234e38f;
+    const float uniform = 1.0f / (float)K;
     for (int k = 0; k < K; ++k) {
         idx[v * K + k] = bi[k];
-        weights[v * K + k] = w[k] / sum;
+        weights[v * K + k] = ok ? w[k] / sum : uniform;
     }
 }
 
@@ -280,7 +295,10 @@ int dm4d_cg_batched_f64(int32_t V, int32_t S, const int32_t *csr_offsets, const 
         DM4D_HIP_CHECK(hipStreamSynchronize(st));
         rel2 = 0.0;
         for (unsigned k = 0; k < sgrid.x; ++k) rel2 = host_worst[k] > rel2 ? host_worst[k] : rel2;
-        if (!(rel2 == rel2)) { set_error("cg: NaN residual after %d iterations (is the matrix positive semi-definite?)", it); return DM4D_ERR_INVALID; }
+        if (!(rel2 <= 1.7976931348623157e308)) {
+            set_error("cg: NaN or infinite residual after %d iterations (a NaN in B, X or the matrix? is the matrix positive semi-definite?)", it);
+            return DM4D_ERR_INVALID;
+        }
         if (rel2 <= tol * tol) break;
     }
     if (final_rel_residual) *final_rel_residual = sqrt(rel2);

@@ -604,7 +604,13 @@ int dm4d_laplacian_smoothing_backward(int32_t T, int32_t V, const int32_t *csr_o
  * (potpourri3d, un-vendored); here the M nodes are the sources of one [M,V] relaxation over the mesh edges.
  * Static inputs (device): one-ring CSR csr_offsets [V+1] / neighbors [E] / edge_lengths [E]; verts [V,3];
  * node_xyz [M,3]; node_vertex [M] = the mesh vertex nearest to each node (:806-812).  scratch:
- * dm4d_graph_geodesic_scratch_bytes.  Synchronises the stream (convergence test). */
+ * dm4d_graph_geodesic_scratch_bytes.  Synchronises the stream (convergence test).
+ * On return the first M * V floats of scratch hold the distance table, node-major [M][V] (float32): the fixed point of
+ * d[v] = min(d[v], d[u] + len(u, v)) from 0 at node_vertex[m]; 3.0e38 where no path reaches.  The fixed point does not depend
+ * on the order of the updates, so the table is bit-reproducible; the tests read it.
+ * Neighbours are the K smallest entries of a vertex's column, ties towards the lower node index (unreachable nodes in index
+ * order).  A row whose K + 1 chosen nodes are equidistant from the vertex, or lie on it, gets the uniform weights 1 / K (the
+ * formula above is 0 / 0 there); weights are always finite and indices always in [0, M).  K <= 16, M > K. */
 size_t dm4d_graph_geodesic_scratch_bytes(int32_t V, int32_t M);
 int dm4d_graph_geodesic_knn(int32_t V, int32_t M, int32_t K, const int32_t *csr_offsets, const int32_t *neighbors,
                             const float *edge_lengths, const float *verts, const float *node_xyz, const int32_t *node_vertex,
@@ -857,7 +863,9 @@ int dm4d_linear_f16(int64_t M, int32_t K, int32_t N, const void *x, const void *
  * X holds the initial guess on entry.  diag_inv [V] = 1 / diagonal.  Stops when every column's |r| / |b| <= tol or after
  * max_iter iterations; the residual is looked at (one host sync) every check_every iterations.  All reductions are
  * two-stage and in fixed order: bit-reproducible.  Returns the number of iterations run (>= 0) or a negative error;
- * *final_rel_residual (host, optional) = the worst column's |r| / |b|. */
+ * *final_rel_residual (host, optional) = the worst column's |r| / |b| (a column with b = 0 counts as converged).  A NaN or an
+ * infinite residual in any column (a NaN in B, X or the matrix) ends the call with DM4D_ERR_INVALID at the next look.  At most
+ * 65,536 right-hand sides per call (DM4D_ERR_UNSUPPORTED above). */
 size_t dm4d_cg_batched_scratch_bytes(int32_t V, int32_t S);
 int dm4d_cg_batched_f64(int32_t V, int32_t S, const int32_t *csr_offsets, const int32_t *csr_cols, const double *csr_vals,
                         const double *diag_inv, const double *B, double *X, void *scratch, int32_t max_iter, double tol,
@@ -867,7 +875,9 @@ int dm4d_cg_batched_f64(int32_t V, int32_t S, const int32_t *csr_offsets, const 
 int dm4d_heat_face_directions(int32_t F, int32_t S, const int32_t *faces, const double *G, const double *U, double *XT, dm4d_stream_t stream);
 /* For the S source vertices first_vertex .. first_vertex + S - 1: the K nearest of M nodes by score[m * ld + s] (smaller =
  * nearer; ties to the lower node index) and the reference's weights (1 - e_k / e_{K+1})^2 of the EUCLIDEAN distances to the node
- * positions, rows normalised (:842-861); neighbor_idx [V,K] int64 / neighbor_weights [V,K] are indexed by vertex. */
+ * positions, rows normalised (:842-861); neighbor_idx [V,K] int64 / neighbor_weights [V,K] are indexed by vertex.  The order is
+ * numpy's stable argsort: +inf after every finite score, NaN after +inf; whatever the scores hold, every index lies in [0, M).
+ * A row whose K + 1 nodes are equidistant from the vertex or lie on it gets the uniform weights 1 / K (0 / 0 in the formula). */
 int dm4d_graph_select_knn(int32_t S, int32_t M, int32_t K, const double *score, int32_t ld, int32_t first_vertex, const float *verts,
                           const float *node_xyz, int64_t *neighbor_idx, float *neighbor_weights, dm4d_stream_t stream);
 
