@@ -1,4 +1,5 @@
-"""ctypes binding of libdm4d_hip.so (C ABI: include/dm4d.h, and include/dm4d_isosurface.h for the mesh-extraction entry points).
+"""ctypes binding of libdm4d_hip.so (C ABI: include/dm4d.h, include/dm4d_isosurface.h for the mesh-extraction entry points and
+include/dm4d_density.h for adaptive density control).
 
 The product path has NO fallback: if the HIP library is missing or fails to load,
 importing an operator raises.  (The CPU restatements under oracle/ are test
@@ -126,6 +127,12 @@ with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d_isosurface.h")) 
 ISO_RECORD_FLOATS = _ISO_CONSTANTS["DM4D_ISO_RECORD_FLOATS"]
 ISO_MAX_RESOLUTION = _ISO_CONSTANTS["DM4D_ISO_MAX_RESOLUTION"]
 
+# likewise adaptive density control
+with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d_density.h")) as _f:
+    _DC_CONSTANTS, _DC_STRUCTS, _DC_SIGNATURES = parse_header(_f.read())
+globals().update({k: v for k, v in _DC_CONSTANTS.items() if k.startswith("DM4D_DC_")})      # _lib.DM4D_DC_SPLIT, ...
+DcArrays = _DC_STRUCTS["dm4d_dc_arrays"]
+
 
 def declared_symbols():
     """Every function include/dm4d.h declares."""
@@ -147,6 +154,16 @@ def iso_abi_version() -> int:
     return _ISO_CONSTANTS["DM4D_ISO_ABI_VERSION"]
 
 
+def dc_declared_symbols():
+    """Every function include/dm4d_density.h declares."""
+    return sorted(_DC_SIGNATURES)
+
+
+def dc_abi_version() -> int:
+    """DM4D_DC_ABI_VERSION of include/dm4d_density.h."""
+    return _DC_CONSTANTS["DM4D_DC_ABI_VERSION"]
+
+
 def build(force: bool = False) -> str:
     """Compile libdm4d_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -165,7 +182,7 @@ def lib() -> C.CDLL:
                 f"{SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  dreammesh4d_amd has no CPU fallback.")
         L = C.CDLL(SO_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_ISO_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_ISO_SIGNATURES.items()) + list(_DC_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -176,6 +193,9 @@ def lib() -> C.CDLL:
         if L.dm4d_iso_version() != iso_abi_version():
             raise ImportError(f"{SO_PATH} has isosurface ABI version {L.dm4d_iso_version()}, include/dm4d_isosurface.h declares "
                               f"{iso_abi_version()}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+        if L.dm4d_dc_version() != dc_abi_version():
+            raise ImportError(f"{SO_PATH} has density-control ABI version {L.dm4d_dc_version()}, include/dm4d_density.h declares "
+                              f"{dc_abi_version()}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
         _LIB = L
     return _LIB
 

@@ -23,6 +23,10 @@ REFERENCE's names (prefix "" -- they replace the CUDA-backed plugins; pass a pre
 """
 from . import threestudio_host as host
 
+# The classes threestudio_host itself defines.  A class that another module registers when it is imported (gaussian_model's
+# `gaussian-splatting`) is kept in `threestudio_host.__extensions__`, is found by `threestudio_host.find`, is listed with the rest
+# by `threestudio_host.registered()`, and is NOT in this table: `register()` below enters PLUGINS into a real threestudio, where
+# the reference's own `gaussian-splatting` already holds that name.
 PLUGINS = dict(host.__modules__)
 
 

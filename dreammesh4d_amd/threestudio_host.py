@@ -7,6 +7,8 @@ into its nested ``Config`` dataclass, sets ``self.device``, calls ``self.configu
 ``update_step(epoch, global_step, on_load_weights)`` (threestudio/utils/base.py:21-57,70-118).  This module provides
 
 * ``register(name)`` / ``find(name)``          -- the registry, pre-populated under the REFERENCE's names with the classes below
+                                                 (a class another module registers on import, ``gaussian_model``'s
+                                                 ``gaussian-splatting``, is kept beside them and found the same way)
 * ``parse_structured(Config, cfg)``           -- dataclass from a dict: unknown keys raise, as OmegaConf's structured mode does
 * ``resolve(root)``                           -- the ``${a.b}`` references and the resolvers the reference registers
                                                  (threestudio/utils/config.py:11-28) on a plain nested dict
@@ -46,16 +48,28 @@ from . import sugar as _sugar
 from . import zero123 as _z
 
 __modules__ = {}
+# classes that OTHER modules register when they are imported (gaussian_model: ``gaussian-splatting``).  ``find`` looks here too;
+# ``__modules__`` -- and with it ``plugins.PLUGINS`` -- stays the table of this module's own classes, whatever has been imported.
+__extensions__ = {}
 
 
 def register(name):
     def decorator(cls):
-        if name in __modules__:
+        if name in __modules__ or name in __extensions__:
             raise ValueError(f"Module {name} already exists! Names of extensions conflict!")
-        __modules__[name] = cls
+        (__modules__ if cls.__module__ == __name__ else __extensions__)[name] = cls
         return cls
 
     return decorator
+
+
+def _registered(name):
+    return __modules__[name] if name in __modules__ else __extensions__[name]
+
+
+def registered():
+    """Every registered name -> class, this module's own and the ones other modules registered, as one dict (a copy)."""
+    return {**__modules__, **__extensions__}
 
 
 def find(name):
@@ -63,8 +77,8 @@ def find(name):
     if ":" in name:
         main_name, sub_name = name.split(":")
         name_list = sub_name.split(",") + [main_name]
-        return type(f"{main_name}.{sub_name}", tuple(__modules__[n] for n in name_list), {})
-    return __modules__[name]
+        return type(f"{main_name}.{sub_name}", tuple(_registered(n) for n in name_list), {})
+    return _registered(name)
 
 
 # ------------------------------------------------------------------------------------------------ config
