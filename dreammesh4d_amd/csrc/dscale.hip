@@ -74,7 +74,7 @@ __global__ __launch_bounds__(kDsThreads) void k_vscale_bwd(int V, int K, int M, 
             for (int j = 0; j < 6; ++j) dot += sym[j] * d[j];
             float lw = 0.f;
             for (int k = 0; k < K; ++k) lw += w[(size_t)v * K + k] * ds_sigmoid(dop[(size_t)f * M + idx[(size_t)v * K + k]]);
-            go += wk * (dot - ((lw + 0.4f < 1.0f) ? tr : 0.f));
+            go += wk * (dot - ((lw + 0.4f <= 1.0f) ? tr : 0.f));      // torch.clamp passes the gradient at the bound
         }
     }
     float *o_ds = g_ds + ((size_t)f * M + m) * 6;

@@ -50,7 +50,16 @@ struct SdsArgs {
 };
 
 typedef _Float16 h16;
-__device__ __forceinline__ h16 hmulf(h16 a, float b) { return (h16)((float)a * b); }
+// The float32 result of a torch float16 operator, rounded to float16 AS A STEP OF ITS OWN.  Without the barrier the compiler folds a
+// multiply and the conversion into one v_fma_mixlo_f16, which rounds the exact product once: where the float32 product lies exactly
+// between two float16 numbers (one element in 2^13) that is the other neighbour than torch's two roundings give
+// (tests/test_dynamic_glue_edges_gpu.py found it in dL/dmean: 1 of 576 and 4 of 12288 elements one float16 ulp off).
+__device__ __forceinline__ h16 round_h16(float x)
+{
+    asm volatile("" : "+v"(x));
+    return (h16)x;
+}
+__device__ __forceinline__ h16 hmulf(h16 a, float b) { return round_h16((float)a * b); }
 
 // std = exp(0.5 clamp(logvar)) and the clamp's gradient mask, rounded where the torch graph rounds
 __device__ __forceinline__ h16 sds_std(h16 logvar, bool &inside)
@@ -58,8 +67,8 @@ __device__ __forceinline__ h16 sds_std(h16 logvar, bool &inside)
     const float lv = (float)logvar;
     inside = lv >= -30.0f && lv <= 20.0f;                        // clamp backward: the gradient passes where min <= x <= max
     const h16 c = (h16)fminf(fmaxf(lv, -30.0f), 20.0f);
-    const h16 half_lv = (h16)(0.5f * (float)c);
-    return (h16)expf((float)half_lv);
+    const h16 half_lv = round_h16(0.5f * (float)c);
+    return round_h16(expf((float)half_lv));
 }
 
 __global__ __launch_bounds__(256) void k_sds_prepare(SdsArgs a)
@@ -77,12 +86,12 @@ __global__ __launch_bounds__(256) void k_sds_prepare(SdsArgs a)
         const h16 mean = a.moments[sds_off(a.sm, b, c, y, x)];
         bool inside;
         const h16 sd = sds_std(a.moments[sds_off(a.sm, b, 4 + c, y, x)], inside);
-        const h16 e = (h16)((float)sd * (float)a.post[sds_off(a.sp, b, c, y, x)]);
-        const h16 s = (h16)((float)mean + (float)e);
-        const float lat = (float)(h16)(a.scale_factor * (float)s);
+        const h16 e = round_h16((float)sd * (float)a.post[sds_off(a.sp, b, c, y, x)]);
+        const h16 s = round_h16((float)mean + (float)e);
+        const float lat = (float)round_h16(a.scale_factor * (float)s);
         a.latents[sds_off(a.sl, b, c, y, x)] = lat;
         const float noisy = sa * lat + sb * a.noise[sds_off(a.sn, b, c, y, x)];
-        const h16 nh = (h16)noisy;
+        const h16 nh = round_h16(noisy);
         a.x_in[sds_off(a.sx, b, c, y, x)] = nh;
         a.x_in[sds_off(a.sx, a.B + b, c, y, x)] = nh;
         a.x_in[sds_off(a.sx, b, 4 + c, y, x)] = (h16)0.0f;
@@ -118,12 +127,12 @@ __global__ __launch_bounds__(1024) void k_sds_finish(SdsArgs a)
             sum_g = __builtin_fmaf(g, g, sum_g);
             // backward of the first block for an upstream gradient of 1 (float16 where the torch graph is float16)
             const float d_lat = (2.0f * diff) * cmul;
-            const h16 dh = (h16)d_lat;
+            const h16 dh = round_h16(d_lat);
             const h16 d_sum = hmulf(dh, a.scale_factor);
             bool inside;
             const h16 sd = sds_std(a.moments[sds_off(a.sm, b, 4 + c, y, x)], inside);
-            const h16 d_std = (h16)((float)d_sum * (float)a.post[sds_off(a.sp, b, c, y, x)]);
-            const h16 d_half = (h16)((float)d_std * (float)sd);                      // exp backward: grad * result
+            const h16 d_std = round_h16((float)d_sum * (float)a.post[sds_off(a.sp, b, c, y, x)]);
+            const h16 d_half = round_h16((float)d_std * (float)sd);                      // exp backward: grad * result
             const h16 d_lv = hmulf(d_half, 0.5f);
             a.d_moments[sds_off(a.sd, b, c, y, x)] = d_sum;
             a.d_moments[sds_off(a.sd, b, 4 + c, y, x)] = inside ? d_lv : (h16)0.0f;

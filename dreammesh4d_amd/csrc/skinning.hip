@@ -329,7 +329,7 @@ __global__ __launch_bounds__(kSkinThreads) void k_skin_bwd_vertex(SkinArgs a0, c
             eta = fminf(eta_raw + 0.4f, 1.0f);
             g_lbs = eta * gx;
             g_dqs = (1.f - eta) * gx;
-            g_eta = (eta_raw + 0.4f < 1.0f) ? dot(gx, x_lbs - x_dqs) : 0.f;
+            g_eta = (eta_raw + 0.4f <= 1.0f) ? dot(gx, x_lbs - x_dqs) : 0.f;      // torch.clamp passes the gradient at the bound
         }
         // x_dqs = R(rh) p + (2 dh * conj(rh)).xyz
         q4 g_rh = a.pypose ? qact_grad_q_pp(rh, p, g_dqs) : qact_grad_q(rh, p, g_dqs);     // q_r.matrix() of transform_point_simple
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(kSkinThreads) void k_skin_bwd_vertex_k4(SkinArgs a0
             eta = fminf(eta_raw + 0.4f, 1.0f);
             g_lbs = eta * gx;
             g_dqs = (1.f - eta) * gx;
-            g_eta = (eta_raw + 0.4f < 1.0f) ? dot(gx, x_lbs - x_dqs) : 0.f;
+            g_eta = (eta_raw + 0.4f <= 1.0f) ? dot(gx, x_lbs - x_dqs) : 0.f;      // torch.clamp passes the gradient at the bound
         }
         q4 g_rh = a.pypose ? qact_grad_q_pp(rh, p, g_dqs) : qact_grad_q(rh, p, g_dqs);     // q_r.matrix() of transform_point_simple
         const q4 G = q4{g_dqs.x, g_dqs.y, g_dqs.z, 0.f};

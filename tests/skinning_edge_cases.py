@@ -2,7 +2,8 @@
 
 The skinning kernels (dreammesh4d_amd/csrc/skinning.hip) switch between a series and a generic formula at hard-coded
 magnitudes (1.19e-7 in so3_log / so3_exp, 1e-4 in so3_log_grad, 1e-3 in so3_exp_grad / row_times_Jl / row_times_Jl_inv),
-evaluate atanf(u / w) for either sign of w, and clamp the hybrid blend at eta + 0.4 = 1.  The scenes here put node rotations
+evaluate atanf(u / w) for either sign of w, and clamp the hybrid blend at eta + 0.4f = 1 (torch.clamp passes the gradient AT the
+bound: `clamp_equality_scene` has two vertices exactly there, in float32 and in float64).  The scenes here put node rotations
 (and, for the face kernels, vertex rotations) into one MAGNITUDE CLASS per node around each of those points, wire the graph
 so that half the vertices have all K neighbours in ONE class (the blended rotation vector sum_k w_k Log q_k then lies in the
 band as well: so3_exp_grad / row_times_Jl see the blend, not the node) and the other half mix classes, leave some nodes
@@ -30,7 +31,9 @@ BANDS = {"eps": (1e-9, 1e-6),        # around kEps = 1.19e-7 after normalisation
 CLASSES = ["zero", "eps", "1e-4", "1e-3", "above_1e-3", "0.15", "1", "3", "w0"]
 N_UNREF = 6                          # the last nodes of every graph are referenced by no vertex
 DQS_MIN_BLEND = 0.25                 # |sum_k w_k q_k| below this: the reference's own singularity (antipodal neighbours), left out
-CLAMP_EXCLUDE = 1e-6                 # |eta + 0.4 - 1| below this: the clamp's side is undecidable in float32
+CLAMP_EXCLUDE = 1e-6                 # 0 < |eta + 0.4f - 1| below this: the clamp's side is undecidable in float32 (exactly 0 is decidable)
+C04 = float(np.float32(0.4))         # the kernels' 0.4f, widened
+W_EQ = np.float32(3355443 * 2.0 ** -24)     # w = (1, W_EQ) on two nodes of opacity sigmoid(0) = 0.5: eta + 0.4f == 1 in both precisions
 
 
 def class_rows(name, n, rng):
@@ -87,6 +90,21 @@ def skin_scene(classes, K, V, M=150, seed=0, hub=False):
             "ds": (0.05 * rng.normal(size=(M, 6))).astype(np.float32), "do": do}
 
 
+def clamp_equality_scene(K, seed=60):
+    """A small scene of large rotations (x_lbs and x_dqs differ by a tenth of the mesh) with two vertices exactly AT the hybrid clamp:
+    nodes 0 and 1 have the opacity logit 0 (sigmoid(0) = 0.5 exactly), the vertices sc["eq_vertices"] name them in their first two
+    slots with the weights (1, W_EQ) and zero weights in the others, so 0.5 + 0.5 W_EQ + 0.4f == 1 exactly in float64 on the widened
+    inputs and 1.0f in float32 in the kernels' order of additions (tests/test_skinning_edges_cpu.py asserts both)."""
+    sc = skin_scene(["1", "0.15"], K, 40, M=14 + N_UNREF, seed=seed + K)
+    sc["do"][:2] = 0.0
+    sc["eq_vertices"] = np.asarray([3, 22])
+    for v in sc["eq_vertices"]:
+        sc["nbr_idx"][v, :2] = (0, 1)
+        sc["nbr_w"][v] = 0.0
+        sc["nbr_w"][v, :2] = (1.0, W_EQ)
+    return sc
+
+
 def skin_upstream(sc, method, seed=1, clamp_margin=CLAMP_EXCLUDE):
     """Upstream gradients (g_xyz [V,3], g_rot [V,4]) and the mask of vertices whose position takes part in the comparison.
     g_xyz is zero on the vertices left out (their node gradients would otherwise carry the excluded quantity)."""
@@ -97,8 +115,8 @@ def skin_upstream(sc, method, seed=1, clamp_margin=CLAMP_EXCLUDE):
     if method in ("dqs", "hybrid"):
         keep &= (q[idx] * w[..., None]).sum(1).norm(dim=-1) >= DQS_MIN_BLEND
     if method == "hybrid":
-        eta = (w[..., None] * op[idx]).sum(1)[:, 0] + 0.4
-        keep &= (eta - 1.0).abs() >= clamp_margin
+        eta = (w[..., None] * op[idx]).sum(1)[:, 0] + C04
+        keep &= ((eta - 1.0).abs() >= clamp_margin) | (eta == 1.0)
         sc["eta"] = eta.numpy()
     g = torch.Generator().manual_seed(seed)
     gx = torch.randn(sc["V"], 3, generator=g) * keep[:, None]
@@ -224,6 +242,8 @@ def skin_cases(which):
             yield f"all/K4/V{V}", skin_scene(CLASSES, 4, V, seed=100 + V)
         for K in (4, 5):
             yield f"hub/K{K}", skin_scene(CLASSES, K, 1500, seed=20 + K, hub=True)
+        for K in (2, 4):             # the generic and the DPP-quad backward, each with two vertices exactly at the hybrid clamp
+            yield f"clamp-eq/K{K}", clamp_equality_scene(K)
     else:
         for K in (1, 4):
             yield f"{which}/K{K}", skin_scene([which], K, 300, seed=10 + K)

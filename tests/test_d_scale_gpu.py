@@ -1,7 +1,8 @@
 """-m gpu: the reference's `d_scale: true` branch (C/geometry/dynamic_sugar.py:593-611 vertex scale matrices, :697-704 Gaussian
 scales, :717-720 the scales handed to the rasterizer): the device operators against the float64 restatement in
 oracle/skinning.py (values and gradients), per-frame scales through the batched-view path against the per-view operator, and
-the `dynamic-sugar` plugin constructed with `d_scale: true`."""
+the `dynamic-sugar` plugin constructed with `d_scale: true`.  One full-size scene and the wiring; the edges (the hybrid clamp on
+both sides and at equality, adjacency extremes, saturated opacity, null outputs) are in tests/test_dynamic_glue_edges_gpu.py."""
 import numpy as np
 import pytest
 import torch

@@ -257,7 +257,9 @@ def test_image_head_equals_the_torch_composition(H, W, C):
     """image_head (csrc/imagehead.hip) against what it replaces in DynamicStage.iteration: clamp(render, 0, 1); MSE against the
     reference images / masks on the reference views (system/sugar_4dgen.py:164-172); the random views resized to half the size with
     bilinear interpolation (the guidance's first step at 512 x 512) -- values, and the gradients on the renderer's colour and alpha
-    images including torch.clamp's pass-through at the bounds (pixels at exactly 0 and 1 are in the data)."""
+    images including torch.clamp's pass-through at the bounds (pixels at exactly 0 and 1 are in the data).  Full size and wiring;
+    the edges (ragged tails, the workgroup cap, view roles, null pointers, the neighbours of 0 and 1) are in
+    tests/test_dynamic_glue_edges_gpu.py."""
     _need_gpu()
     import torch.nn.functional as F
 

@@ -1,5 +1,6 @@
 """loss_sum (csrc/imagehead.hip: dm4d_weighted_sum*, dm4d_partial_sums) against the torch expressions it replaces
-(system/sugar_4dgen.py:296-330, sugar_static.py:246-340: `loss = lambda_a * a + lambda_b * b + ...` on 0-dim tensors)."""
+(system/sugar_4dgen.py:296-330, sugar_static.py:246-340: `loss = lambda_a * a + lambda_b * b + ...` on 0-dim tensors).
+The wiring and the limits; every size of k_partial_sums and the edges of the weighted sum are in tests/test_dynamic_glue_edges_gpu.py."""
 import pytest
 import torch
 

@@ -155,6 +155,36 @@ def test_hybrid_scenes_straddle_the_clamp_and_exclude_next_to_nothing():
         assert ((d > 0) & (d < 1e-3)).sum() >= 10 and ((d < 0) & (d > -1e-3)).sum() >= 10, label
 
 
+def test_clamp_equality_vertices_sit_exactly_at_the_clamp_and_keep_their_gradient():
+    """eta + 0.4f == 1 exactly, in float64 on the widened inputs and in float32 in the kernels' order of additions; such a vertex is
+    NOT left out (only 0 < |eta + 0.4f - 1| < 1e-6 is), torch.clamp passes the gradient there, and the float64 oracle (whose double
+    0.4 puts it 6e-9 below the bound) passes it too: dL/d(d_opacity) of the two nodes carries the vertices' x_lbs - x_dqs term."""
+    x = torch.tensor(np.float32(0.6), requires_grad=True)
+    torch.clamp(x + 0.4, max=1.0).backward()
+    assert x.grad.item() == 1.0
+    for K in (2, 4):
+        sc = ec.clamp_equality_scene(K)
+        eq = sc["eq_vertices"]
+        gx, gr, keep = ec.skin_upstream(sc, "hybrid")
+        assert (sc["eta"][eq] == 1.0).all() and keep[eq].all() and float(gx[eq].abs().min()) > 0
+        near = (np.abs(sc["eta"] - 1.0) < ec.CLAMP_EXCLUDE) & (sc["eta"] != 1.0)
+        assert not keep[near].any()
+        h, c04 = np.float32(0.5), np.float32(0.4)
+        assert (sc["do"][:2] == 0).all() and 1.0 / (1.0 + np.exp(-np.float32(0))) == 0.5
+        for v in eq:
+            w = sc["nbr_w"][v]
+            acc = np.float32(0)
+            for k in range(K):                                   # skinning.hip: eta += w * o, slot by slot; quad_sum adds the same two
+                acc = np.float32(acc + np.float32(w[k] * h))     # non-zero terms
+            assert np.float32(acc + c04) == np.float32(1.0) and not w[2:].any()
+        # the gradient the `<` form dropped: with the equality vertices' upstream gradient alone, dL/d(d_opacity) of nodes 0 and 1
+        only = torch.zeros_like(gx)
+        only[eq] = gx[eq]
+        _, _, g = ec.skin_reference(sc, "hybrid", "exact", only, torch.zeros_like(gr))
+        s = ec.skin_row_scale(sc, only, torch.zeros_like(gr))
+        assert (np.abs(g["do"][:2, 0]) > 100 * ec.KERNEL_BOUND * s[:2]).all(), (g["do"][:2, 0], s[:2])
+
+
 def _floor_cases():
     for which in ["all"] + ec.CLASSES:
         yield from ((which, "skin", l, s) for l, s in ec.skin_cases(which))

@@ -7,8 +7,9 @@ one call and each class alone; K in {1, 2, 3, 4, 5, 8}; K = 4 with V in {1, 63, 
 DPP-quad kernel); unreferenced nodes (gradient exactly 0), a node referenced by every vertex, zero weights; the hybrid blend
 on both sides of and next to its clamp; upstream gradients absent (null pointers); zero-area faces.
 Left out, because the REFERENCE is singular there: vertices whose blended real dual-quaternion part sum_k w_k q_k has norm
-< 0.25 (antipodal neighbours nearly cancel), vertices with |eta + 0.4 - 1| < 1e-6 (at most 0.5 % of a scene, asserted on
-the CPU), the zero-area faces' normal gradient (1e12-scale through the 1e-12 clamp; it lands on vertices of their own).
+< 0.25 (antipodal neighbours nearly cancel), vertices with 0 < |eta + 0.4f - 1| < 1e-6 (at most 0.5 % of a scene, asserted on
+the CPU; a vertex EXACTLY at the clamp is decidable and takes part: torch.clamp passes the gradient there, and so must the
+kernels -- `clamp-eq/K2` and `clamp-eq/K4`), the zero-area faces' normal gradient (1e12-scale through the 1e-12 clamp; it lands on vertices of their own).
 
 Asserted: everything finite; forward per element 2e-6 absolute (quaternions as stored: the reference's sign); backward per
 element |hip - ref| <= B (|ref| + s), s = the row's summed upstream-gradient norms, B = 8 x the float32 floor of the oracle's
@@ -110,6 +111,30 @@ def test_skin_vertices_at_branch_points(which, mode):
         for method in ec.METHODS:
             _skin_case(sc, label, method, mode, report)
     _judge(report)
+
+
+@pytest.mark.parametrize("K", [2, 4])
+def test_hybrid_clamp_equality_vertices_pass_the_gradient(K):
+    """Two vertices with eta + 0.4f == 1 exactly (tests/skinning_edge_cases.py::clamp_equality_scene), in the generic (K = 2) and the
+    DPP-quad (K = 4) backward, with the upstream gradient on those two vertices alone: dL/d(d_opacity) of their nodes is the
+    x_lbs - x_dqs term that torch.clamp's backward passes at the bound."""
+    _need_gpu()
+    from dreammesh4d_amd import ops
+
+    sc = ec.clamp_equality_scene(K)
+    graph = ops.DeformGraph(sc["verts"], sc["nbr_idx"], sc["nbr_w"], sc["M"], torch.device("cuda:0"))
+    gx, gr, keep = ec.skin_upstream(sc, "hybrid")
+    assert keep[sc["eq_vertices"]].all()
+    only = torch.zeros_like(gx)
+    only[sc["eq_vertices"]] = gx[sc["eq_vertices"]]
+    gr = torch.zeros_like(gr)
+    s = ec.skin_row_scale(sc, only, gr)
+    for mode in ec.MODES:
+        _, _, og = ec.skin_reference(sc, "hybrid", mode, only, gr)
+        _, _, g = _skin_hip(sc, graph, "hybrid", mode, only, gr)
+        r = ec.skin_ratios(sc, "hybrid", g, og, s)
+        print(f"clamp-eq/K{K}/{mode}", {k: f"{v:.2e}" for k, v in r.items()}, "d_opacity of nodes 0, 1: hip", g["do"][:2, 0], "float64", og["do"][:2, 0], flush=True)
+        assert max(r.values()) <= ec.KERNEL_BOUND, (mode, r, g["do"][:2, 0], og["do"][:2, 0])
 
 
 @pytest.mark.parametrize("mode", ec.MODES)

@@ -145,7 +145,9 @@ def test_fused_glue_kernels_equal_the_torch_operators_between_the_networks(clip)
 def test_glue_kernels_element_by_element_against_torch_autograd():
     """dm4d_sds_prepare / dm4d_sds_finish alone, on random float16 moments (log-variance on both sides of the lower clamp) and a
     random "UNet prediction", against the torch operators with autograd: latents and the UNet's input bit-identical, loss and
-    |grad| to 1e-6, dL/dmoments identical except for isolated elements (<= 0.1 %) at most two float16 ulps apart."""
+    |grad| to 1e-6, dL/dmoments identical except for isolated elements (<= 0.1 %) at most two float16 ulps apart.  The full size on
+    the device's own torch; the edges (non-square shapes, the clamp bounds, NaN / inf predictions, |g| == clip, strided tensors) are
+    in tests/test_dynamic_glue_edges_gpu.py against a CPU restatement."""
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
     import ctypes as C_
