@@ -1,5 +1,5 @@
-"""ctypes binding of libdm4d_hip.so (C ABI: include/dm4d.h, include/dm4d_isosurface.h for the mesh-extraction entry points and
-include/dm4d_density.h for adaptive density control).
+"""ctypes binding of libdm4d_hip.so (C ABI: include/dm4d.h, include/dm4d_isosurface.h for the mesh-extraction entry points,
+include/dm4d_density.h for adaptive density control and include/dm4d_sugar_reg.h for the SuGaR regularisation).
 
 The product path has NO fallback: if the HIP library is missing or fails to load,
 importing an operator raises.  (The CPU restatements under oracle/ are test
@@ -133,6 +133,11 @@ with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d_density.h")) as 
 globals().update({k: v for k, v in _DC_CONSTANTS.items() if k.startswith("DM4D_DC_")})      # _lib.DM4D_DC_SPLIT, ...
 DcArrays = _DC_STRUCTS["dm4d_dc_arrays"]
 
+# and the SuGaR density and normal regularisation
+with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d_sugar_reg.h")) as _f:
+    _SR_CONSTANTS, _SR_STRUCTS, _SR_SIGNATURES = parse_header(_f.read())
+globals().update({k: v for k, v in _SR_CONSTANTS.items() if k.startswith("DM4D_SR_")})      # _lib.DM4D_SR_CHUNK, ...
+
 
 def declared_symbols():
     """Every function include/dm4d.h declares."""
@@ -164,6 +169,16 @@ def dc_abi_version() -> int:
     return _DC_CONSTANTS["DM4D_DC_ABI_VERSION"]
 
 
+def sr_declared_symbols():
+    """Every function include/dm4d_sugar_reg.h declares."""
+    return sorted(_SR_SIGNATURES)
+
+
+def sr_abi_version() -> int:
+    """DM4D_SR_ABI_VERSION of include/dm4d_sugar_reg.h."""
+    return _SR_CONSTANTS["DM4D_SR_ABI_VERSION"]
+
+
 def build(force: bool = False) -> str:
     """Compile libdm4d_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -182,7 +197,8 @@ def lib() -> C.CDLL:
                 f"{SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  dreammesh4d_amd has no CPU fallback.")
         L = C.CDLL(SO_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_ISO_SIGNATURES.items()) + list(_DC_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_ISO_SIGNATURES.items()) + list(_DC_SIGNATURES.items()) \
+                + list(_SR_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -196,6 +212,9 @@ def lib() -> C.CDLL:
         if L.dm4d_dc_version() != dc_abi_version():
             raise ImportError(f"{SO_PATH} has density-control ABI version {L.dm4d_dc_version()}, include/dm4d_density.h declares "
                               f"{dc_abi_version()}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+        if L.dm4d_sr_version() != sr_abi_version():
+            raise ImportError(f"{SO_PATH} has SuGaR-regularisation ABI version {L.dm4d_sr_version()}, include/dm4d_sugar_reg.h declares "
+                              f"{sr_abi_version()}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
         _LIB = L
     return _LIB
 
