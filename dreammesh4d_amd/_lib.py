@@ -1,5 +1,6 @@
 """ctypes binding of libdm4d_hip.so (C ABI: include/dm4d.h, include/dm4d_isosurface.h for the mesh-extraction entry points,
-include/dm4d_density.h for adaptive density control and include/dm4d_sugar_reg.h for the SuGaR regularisation).
+include/dm4d_density.h for adaptive density control, include/dm4d_sugar_reg.h for the SuGaR regularisation and
+include/dm4d_mesh_clean.h for mesh cleaning).
 
 The product path has NO fallback: if the HIP library is missing or fails to load,
 importing an operator raises.  (The CPU restatements under oracle/ are test
@@ -138,6 +139,11 @@ with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d_sugar_reg.h")) a
     _SR_CONSTANTS, _SR_STRUCTS, _SR_SIGNATURES = parse_header(_f.read())
 globals().update({k: v for k, v in _SR_CONSTANTS.items() if k.startswith("DM4D_SR_")})      # _lib.DM4D_SR_CHUNK, ...
 
+# and mesh cleaning
+with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d_mesh_clean.h")) as _f:
+    _MCL_CONSTANTS, _MCL_STRUCTS, _MCL_SIGNATURES = parse_header(_f.read())
+globals().update({k: v for k, v in _MCL_CONSTANTS.items() if k.startswith("DM4D_MCL_")})    # _lib.DM4D_MCL_STATE_WORDS, ...
+
 
 def declared_symbols():
     """Every function include/dm4d.h declares."""
@@ -179,6 +185,16 @@ def sr_abi_version() -> int:
     return _SR_CONSTANTS["DM4D_SR_ABI_VERSION"]
 
 
+def mcl_declared_symbols():
+    """Every function include/dm4d_mesh_clean.h declares."""
+    return sorted(_MCL_SIGNATURES)
+
+
+def mcl_abi_version() -> int:
+    """DM4D_MCL_ABI_VERSION of include/dm4d_mesh_clean.h."""
+    return _MCL_CONSTANTS["DM4D_MCL_ABI_VERSION"]
+
+
 def build(force: bool = False) -> str:
     """Compile libdm4d_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -198,7 +214,7 @@ def lib() -> C.CDLL:
                 "(hipcc --offload-arch=gfx950).  dreammesh4d_amd has no CPU fallback.")
         L = C.CDLL(SO_PATH)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_ISO_SIGNATURES.items()) + list(_DC_SIGNATURES.items()) \
-                + list(_SR_SIGNATURES.items()):
+                + list(_SR_SIGNATURES.items()) + list(_MCL_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -215,6 +231,9 @@ def lib() -> C.CDLL:
         if L.dm4d_sr_version() != sr_abi_version():
             raise ImportError(f"{SO_PATH} has SuGaR-regularisation ABI version {L.dm4d_sr_version()}, include/dm4d_sugar_reg.h declares "
                               f"{sr_abi_version()}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+        if L.dm4d_mcl_version() != mcl_abi_version():
+            raise ImportError(f"{SO_PATH} has mesh-cleaning ABI version {L.dm4d_mcl_version()}, include/dm4d_mesh_clean.h declares "
+                              f"{mcl_abi_version()}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
         _LIB = L
     return _LIB
 

@@ -13,11 +13,13 @@ triple Python loop over blocks, then ``mcubes.marching_cubes`` on the CPU) with 
   ``3 * voxel + axis``; faces cube by cube in ascending voxel index, in the order of the generated table
   (``tools/gen_mc_table.py`` -> ``csrc/mc_table.h``), normals toward lower field values.
 
-Not restated: the reference's ``clean_mesh(remesh=True)`` and ``decimate_mesh`` (pymeshlab).  The next step here is
+The reference's ``clean_mesh`` up to its repair filters -- unreferenced vertices, null and duplicate faces, small connected
+components -- is ``dreammesh4d_amd.mesh_clean`` (``extract_mesh(..., clean=True)``, ``--clean``).  Not restated: the repair and
+remeshing half of ``clean_mesh(remesh=True)`` and ``decimate_mesh`` (pymeshlab).  The next step here is
 ``python -m dreammesh4d_amd.mesh_simplify``.  The sort of the pair keys and the prefix sums are torch calls on the device;
 everything else is HIP.  There is no CPU path.
 
-    python -m dreammesh4d_amd.isosurface --ply gaussians.ply --resolution 128 --density_thresh 0.8 --output out_dir
+    python -m dreammesh4d_amd.isosurface --ply gaussians.ply --resolution 128 --density_thresh 0.8 --output out_dir [--clean]
 """
 import argparse
 import math
@@ -206,7 +208,7 @@ def _gaussians_of(geometry_or_dict):
     return val("get_xyz"), val("get_scaling"), val("get_rotation"), val("get_opacity"), rgb
 
 
-def extract_mesh(geometry_or_dict, density_thresh=0.8, resolution=128, num_blocks=16):
+def extract_mesh(geometry_or_dict, density_thresh=0.8, resolution=128, num_blocks=16, clean=False, min_f=64, min_d=20.0, keep="all"):
     """The coloured mesh of a set of Gaussians: ``gaussian_density_field`` then ``marching_cubes`` at ``density_thresh``, vertices
     back in world coordinates ``(v / (R - 1) * 2 - 1) / scale + center``.
 
@@ -216,8 +218,11 @@ def extract_mesh(geometry_or_dict, density_thresh=0.8, resolution=128, num_block
 
     -> dict(verts [V,3] float32, faces [F,3] int64, colors [V,3] float32 or None, n_kept, n_pairs, center, scale).
 
-    The reference's ``extract_mesh`` goes on to ``clean_mesh(remesh=True)`` and ``decimate_mesh``, which need pymeshlab; they are
-    not restated.  The next step here is ``dreammesh4d_amd.mesh_simplify``."""
+    The reference's ``extract_mesh`` goes on to ``clean_mesh(remesh=True)`` and ``decimate_mesh``.  ``clean=True`` runs
+    ``mesh_clean.clean_mesh(verts, faces, colors, min_f, min_d, keep)`` on the mesh: verts, faces and colors are then the cleaned
+    ones and the dict also carries vertex_map, face_map, labels, n_components, n_null, n_duplicate and n_small.  The default leaves
+    the output as marching cubes made it.  The repair and remeshing filters and ``decimate_mesh`` need pymeshlab; they are not
+    restated.  The next step here is ``dreammesh4d_amd.mesh_simplify``."""
     with torch.no_grad():
         xyz, scaling, rotation, opacity, rgb = _gaussians_of(geometry_or_dict)
         f32 = lambda t: None if t is None else t.detach().to(torch.float32)
@@ -226,8 +231,13 @@ def extract_mesh(geometry_or_dict, density_thresh=0.8, resolution=128, num_block
         mesh = marching_cubes(field["occ"], density_thresh, field["csum"])
         R = int(resolution)
         verts = (mesh["verts"] / (R - 1.0) * 2 - 1) / field["scale"] + field["center"]
-    return {"verts": verts, "faces": mesh["faces"], "colors": mesh["colors"], "n_kept": field["n_kept"], "n_pairs": field["n_pairs"],
-            "center": field["center"], "scale": field["scale"]}
+    res = {"verts": verts, "faces": mesh["faces"], "colors": mesh["colors"], "n_kept": field["n_kept"], "n_pairs": field["n_pairs"],
+           "center": field["center"], "scale": field["scale"]}
+    if clean:
+        from . import mesh_clean
+
+        res.update(mesh_clean.clean_mesh(verts, mesh["faces"], mesh["colors"], min_f=min_f, min_d=min_d, keep=keep))
+    return res
 
 
 def output_path(ply_path, output):
@@ -236,12 +246,16 @@ def output_path(ply_path, output):
 
 
 def _parser():
+    from . import mesh_clean
+
     p = argparse.ArgumentParser(prog="python -m dreammesh4d_amd.isosurface", description=__doc__.split("\n")[0])
     p.add_argument("--ply", required=True, help="3D Gaussian splatting .ply (the layout of GaussianIO.save_ply)")
     p.add_argument("--resolution", default=128, type=int, help="grid points per axis")
     p.add_argument("--num_blocks", default=16, type=int, help="blocks per axis of the cut-off")
     p.add_argument("--density_thresh", default=0.8, type=float, help="iso value of the occupancy")
     p.add_argument("--output", required=True, help="directory of the output mesh")
+    p.add_argument("--clean", action="store_true", help="remove null and duplicate faces and small components (mesh_clean) before writing")
+    mesh_clean.add_arguments(p)
     return p
 
 
@@ -255,8 +269,10 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
     res = extract_mesh({k: t(g[k]) for k in ("xyz", "scaling", "rotation", "opacity", "rgb")}, density_thresh=args.density_thresh,
-                       resolution=args.resolution, num_blocks=args.num_blocks)
+                       resolution=args.resolution, num_blocks=args.num_blocks, clean=args.clean, min_f=args.min_f, min_d=args.min_d, keep=args.keep)
     print(f"{len(g['xyz'])} Gaussians, {res['n_kept']} kept (opacity > {OPACITY_FLOOR}), {res['n_pairs']} (Gaussian, block) pairs")
+    if args.clean:
+        print(f"{res['n_null']} null and {res['n_duplicate']} duplicate faces, {res['n_components']} components, {res['n_small']} of them small")
     print(f"Extracted mesh has {len(res['verts'])} vertices and {len(res['faces'])} triangles")
     os.makedirs(args.output, exist_ok=True)
     path = output_path(args.ply, args.output)
