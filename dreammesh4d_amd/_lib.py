@@ -1,6 +1,4 @@
-"""ctypes binding of libdm4d_hip.so (C ABI: include/dm4d.h, include/dm4d_isosurface.h for the mesh-extraction entry points,
-include/dm4d_density.h for adaptive density control, include/dm4d_sugar_reg.h for the SuGaR regularisation and
-include/dm4d_mesh_clean.h for mesh cleaning).
+"""ctypes binding of libdm4d_hip.so, derived from the headers of its C ABI under include/ (the table ``HEADERS`` below).
 
 The product path has NO fallback: if the HIP library is missing or fails to load,
 importing an operator raises.  (The CPU restatements under oracle/ are test
@@ -10,6 +8,7 @@ import ctypes as C
 import os
 import re
 import subprocess
+from collections import namedtuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libdm4d_hip.so")
@@ -110,89 +109,50 @@ def parse_header(text, fn_typedefs=None):
     return constants, structs, signatures
 
 
-with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d.h")) as _f:
-    _CONSTANTS, _STRUCTS, _SIGNATURES = parse_header(_f.read(), {"dm4d_alloc_fn": ALLOC_FN})
-globals().update(_CONSTANTS)            # _lib.DM4D_ERR_INVALID, _lib.DM4D_GRAD_PYPOSE, ...
+# One row per header of the C ABI: file under include/, key, the library's version function, the header's version macro, which
+# constants become names of this module (None: all, a tuple of prefixes, or a dict {module name: constant}), and the structs that
+# get a module-level alias {module name: C name}.  Every header keeps its own functions and its own version number.  Adding a
+# header is adding a row.
+Header = namedtuple("Header", "file key version_fn version_macro constants structs")
+HEADERS = tuple(Header(*row) for row in (
+    ("dm4d.h", "dm4d", "dm4d_version", "DM4D_ABI_VERSION", None,
+     {"RasterSettings": "dm4d_raster_settings", "RasterInputs": "dm4d_raster_inputs", "ViewsStruct": "dm4d_views",
+      "ViewsGrads": "dm4d_views_grads", "GViewsStruct": "dm4d_gviews", "GViewsGrads": "dm4d_gviews_grads",
+      "MlpWeights": "dm4d_mlp_weights", "MlpWeightsGrad": "dm4d_mlp_weights_grad", "StepDesc": "dm4d_step_desc",
+      "GradSegments": "dm4d_grad_segments", "AdamwArgs": "dm4d_adamw_args", "AdamwStepArgs": "dm4d_adamw_step_args"}),
+    ("dm4d_isosurface.h", "iso", "dm4d_iso_version", "DM4D_ISO_ABI_VERSION",
+     {"ISO_RECORD_FLOATS": "DM4D_ISO_RECORD_FLOATS", "ISO_MAX_RESOLUTION": "DM4D_ISO_MAX_RESOLUTION"}, {}),
+    ("dm4d_density.h", "dc", "dm4d_dc_version", "DM4D_DC_ABI_VERSION", ("DM4D_DC_",), {"DcArrays": "dm4d_dc_arrays"}),
+    ("dm4d_sugar_reg.h", "sr", "dm4d_sr_version", "DM4D_SR_ABI_VERSION", ("DM4D_SR_",), {}),
+    ("dm4d_mesh_clean.h", "mcl", "dm4d_mcl_version", "DM4D_MCL_ABI_VERSION", ("DM4D_MCL_",), {}),
+))
+_PARSED = {}                            # key -> (constants, structs, signatures)
+for _h in HEADERS:
+    with open(os.path.join(os.path.dirname(_HERE), "include", _h.file)) as _f:
+        _c, _s, _ = _PARSED[_h.key] = parse_header(_f.read(), {"dm4d_alloc_fn": ALLOC_FN})
+    if isinstance(_h.constants, dict):
+        globals().update({k: _c[v] for k, v in _h.constants.items()})                           # _lib.ISO_RECORD_FLOATS
+    else:
+        globals().update({k: v for k, v in _c.items() if _h.constants is None or k.startswith(_h.constants)})     # _lib.DM4D_DC_SPLIT
+    globals().update({k: _s[v] for k, v in _h.structs.items()})                                 # _lib.RasterSettings
+_CONSTANTS, _STRUCTS, _SIGNATURES = _PARSED["dm4d"]
 OK = _CONSTANTS["DM4D_OK"]
 MAX_GRAD_SEGMENTS = _CONSTANTS["DM4D_MAX_GRAD_SEGMENTS"]
-RasterSettings, RasterInputs = _STRUCTS["dm4d_raster_settings"], _STRUCTS["dm4d_raster_inputs"]
-ViewsStruct, ViewsGrads = _STRUCTS["dm4d_views"], _STRUCTS["dm4d_views_grads"]
-GViewsStruct, GViewsGrads = _STRUCTS["dm4d_gviews"], _STRUCTS["dm4d_gviews_grads"]
-MlpWeights, MlpWeightsGrad = _STRUCTS["dm4d_mlp_weights"], _STRUCTS["dm4d_mlp_weights_grad"]
-StepDesc = _STRUCTS["dm4d_step_desc"]
-GradSegments, AdamwArgs, AdamwStepArgs = _STRUCTS["dm4d_grad_segments"], _STRUCTS["dm4d_adamw_args"], _STRUCTS["dm4d_adamw_step_args"]
-
-# the mesh-extraction entry points have a header and a version of their own: include/dm4d.h keeps its functions and its number
-with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d_isosurface.h")) as _f:
-    _ISO_CONSTANTS, _ISO_STRUCTS, _ISO_SIGNATURES = parse_header(_f.read())
-ISO_RECORD_FLOATS = _ISO_CONSTANTS["DM4D_ISO_RECORD_FLOATS"]
-ISO_MAX_RESOLUTION = _ISO_CONSTANTS["DM4D_ISO_MAX_RESOLUTION"]
-
-# likewise adaptive density control
-with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d_density.h")) as _f:
-    _DC_CONSTANTS, _DC_STRUCTS, _DC_SIGNATURES = parse_header(_f.read())
-globals().update({k: v for k, v in _DC_CONSTANTS.items() if k.startswith("DM4D_DC_")})      # _lib.DM4D_DC_SPLIT, ...
-DcArrays = _DC_STRUCTS["dm4d_dc_arrays"]
-
-# and the SuGaR density and normal regularisation
-with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d_sugar_reg.h")) as _f:
-    _SR_CONSTANTS, _SR_STRUCTS, _SR_SIGNATURES = parse_header(_f.read())
-globals().update({k: v for k, v in _SR_CONSTANTS.items() if k.startswith("DM4D_SR_")})      # _lib.DM4D_SR_CHUNK, ...
-
-# and mesh cleaning
-with open(os.path.join(os.path.dirname(_HERE), "include", "dm4d_mesh_clean.h")) as _f:
-    _MCL_CONSTANTS, _MCL_STRUCTS, _MCL_SIGNATURES = parse_header(_f.read())
-globals().update({k: v for k, v in _MCL_CONSTANTS.items() if k.startswith("DM4D_MCL_")})    # _lib.DM4D_MCL_STATE_WORDS, ...
 
 
-def declared_symbols():
-    """Every function include/dm4d.h declares."""
-    return sorted(_SIGNATURES)
+def declared_symbols(header="dm4d"):
+    """Every function the header with key `header` declares."""
+    return sorted(_PARSED[header][2])
 
 
-def abi_version() -> int:
-    """DM4D_ABI_VERSION of include/dm4d.h (the header the binding is derived from)."""
-    return _CONSTANTS["DM4D_ABI_VERSION"]
+def abi_version(header="dm4d") -> int:
+    """The version macro of the header with key `header` (the header the binding is derived from)."""
+    return _PARSED[header][0][next(h.version_macro for h in HEADERS if h.key == header)]
 
 
-def iso_declared_symbols():
-    """Every function include/dm4d_isosurface.h declares."""
-    return sorted(_ISO_SIGNATURES)
-
-
-def iso_abi_version() -> int:
-    """DM4D_ISO_ABI_VERSION of include/dm4d_isosurface.h."""
-    return _ISO_CONSTANTS["DM4D_ISO_ABI_VERSION"]
-
-
-def dc_declared_symbols():
-    """Every function include/dm4d_density.h declares."""
-    return sorted(_DC_SIGNATURES)
-
-
-def dc_abi_version() -> int:
-    """DM4D_DC_ABI_VERSION of include/dm4d_density.h."""
-    return _DC_CONSTANTS["DM4D_DC_ABI_VERSION"]
-
-
-def sr_declared_symbols():
-    """Every function include/dm4d_sugar_reg.h declares."""
-    return sorted(_SR_SIGNATURES)
-
-
-def sr_abi_version() -> int:
-    """DM4D_SR_ABI_VERSION of include/dm4d_sugar_reg.h."""
-    return _SR_CONSTANTS["DM4D_SR_ABI_VERSION"]
-
-
-def mcl_declared_symbols():
-    """Every function include/dm4d_mesh_clean.h declares."""
-    return sorted(_MCL_SIGNATURES)
-
-
-def mcl_abi_version() -> int:
-    """DM4D_MCL_ABI_VERSION of include/dm4d_mesh_clean.h."""
-    return _MCL_CONSTANTS["DM4D_MCL_ABI_VERSION"]
+def all_declared_symbols():
+    """Every function any header of the table declares."""
+    return sorted(name for _, _, signatures in _PARSED.values() for name in signatures)
 
 
 def build(force: bool = False) -> str:
@@ -213,27 +173,15 @@ def lib() -> C.CDLL:
                 f"{SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  dreammesh4d_amd has no CPU fallback.")
         L = C.CDLL(SO_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_ISO_SIGNATURES.items()) + list(_DC_SIGNATURES.items()) \
-                + list(_SR_SIGNATURES.items()) + list(_MCL_SIGNATURES.items()):
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        want = abi_version()
-        if L.dm4d_version() != want:
-            raise ImportError(f"{SO_PATH} has ABI version {L.dm4d_version()}, include/dm4d.h declares {want}: rebuild it "
-                              "(`python -c 'import __graft_entry__ as g; g.build()'`)")
-        if L.dm4d_iso_version() != iso_abi_version():
-            raise ImportError(f"{SO_PATH} has isosurface ABI version {L.dm4d_iso_version()}, include/dm4d_isosurface.h declares "
-                              f"{iso_abi_version()}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-        if L.dm4d_dc_version() != dc_abi_version():
-            raise ImportError(f"{SO_PATH} has density-control ABI version {L.dm4d_dc_version()}, include/dm4d_density.h declares "
-                              f"{dc_abi_version()}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-        if L.dm4d_sr_version() != sr_abi_version():
-            raise ImportError(f"{SO_PATH} has SuGaR-regularisation ABI version {L.dm4d_sr_version()}, include/dm4d_sugar_reg.h declares "
-                              f"{sr_abi_version()}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-        if L.dm4d_mcl_version() != mcl_abi_version():
-            raise ImportError(f"{SO_PATH} has mesh-cleaning ABI version {L.dm4d_mcl_version()}, include/dm4d_mesh_clean.h declares "
-                              f"{mcl_abi_version()}: rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
+        for h in HEADERS:
+            for name, (res, args) in _PARSED[h.key][2].items():
+                fn = getattr(L, name)
+                fn.restype = res
+                fn.argtypes = args
+            have, want = getattr(L, h.version_fn)(), abi_version(h.key)
+            if have != want:
+                raise ImportError(f"{SO_PATH} has ABI version {have} of include/{h.file}, the header declares {want}: rebuild it "
+                                  "(`python -c 'import __graft_entry__ as g; g.build()'`)")
         _LIB = L
     return _LIB
 

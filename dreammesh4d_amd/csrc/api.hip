@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.h"
+#include "hostcheck.h"
 #include "raster.h"
 
 namespace dm4d {
@@ -400,7 +401,8 @@ int dm4d_sh_eval_forward(int32_t N, int32_t degree, int32_t M, const float *mean
     if (N < 0) { set_error("negative N"); return DM4D_ERR_INVALID; }
     const int rc = check_sh(degree, M);
     if (rc) return rc;
-    if (N > 0 && (!means3D || !campos || !shs || !rgb || !clamped)) { set_error("dm4d_sh_eval_forward: null argument"); return DM4D_ERR_INVALID; }
+    const char *fn = "dm4d_sh_eval_forward";
+    DM4D_REFUSE_NULL(N > 0 && (!means3D || !campos || !shs || !rgb || !clamped))
     return launch_sh_eval_forward(N, degree, M, means3D, campos, shs, rgb, clamped, (hipStream_t)stream);
 }
 
@@ -410,10 +412,8 @@ int dm4d_sh_eval_backward(int32_t N, int32_t degree, int32_t M, const float *mea
     if (N < 0) { set_error("negative N"); return DM4D_ERR_INVALID; }
     const int rc = check_sh(degree, M);
     if (rc) return rc;
-    if (N > 0 && (!means3D || !campos || !shs || !clamped || !dL_drgb || !dL_dsh || !dL_dmeans3D)) {
-        set_error("dm4d_sh_eval_backward: null argument");
-        return DM4D_ERR_INVALID;
-    }
+    const char *fn = "dm4d_sh_eval_backward";
+    DM4D_REFUSE_NULL(N > 0 && (!means3D || !campos || !shs || !clamped || !dL_drgb || !dL_dsh || !dL_dmeans3D))
     return launch_sh_eval_backward(N, degree, M, means3D, campos, shs, clamped, nullptr, dL_drgb, dL_dsh, dL_dmeans3D, 0,
                                    (hipStream_t)stream);
 }

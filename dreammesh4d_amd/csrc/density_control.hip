@@ -19,6 +19,7 @@
 //   k_dc_split_children   xyz and _scaling of the child rows
 //   k_dc_reset_opacity
 #include "common.h"
+#include "hostcheck.h"
 #include "../../include/dm4d.h"
 #include "../../include/dm4d_density.h"
 
@@ -332,13 +333,6 @@ __global__ __launch_bounds__(kDcThreads) void k_dc_reset_opacity(const int64_t N
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static bool dc_bad_rows(const char *fn, const char *what, int64_t n, int64_t most)
-{
-    if (n >= 0 && n <= most) return false;
-    set_error("%s: %s = %lld is outside [0, %lld]", fn, what, (long long)n, (long long)most);
-    return true;
-}
-
 static bool dc_bad_children(const char *fn, int32_t S)
 {
     if (S >= 1 && S <= DM4D_DC_MAX_CHILDREN) return false;
@@ -346,19 +340,11 @@ static bool dc_bad_children(const char *fn, int32_t S)
     return true;
 }
 
-static unsigned dc_blocks(int64_t n) { return (unsigned)((n + kDcThreads - 1) / kDcThreads); }
 static int64_t dc_tiles(int64_t n) { return (n + kDcTile - 1) / kDcTile; }
-static int dc_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace dm4d
 
 using namespace dm4d;
-
-#define DC_NULL(cond)                                   \
-    if (cond) {                                         \
-        set_error("%s: null argument", fn);             \
-        return DM4D_ERR_INVALID;                        \
-    }
 
 extern "C" {
 
@@ -368,11 +354,11 @@ int dm4d_dc_accumulate_stats(int32_t B, int64_t N, const void *grad2d, const voi
                              void *stream)
 {
     const char *fn = "dm4d_dc_accumulate_stats";
-    if (dc_bad_rows(fn, "N", N, DM4D_DC_MAX_ROWS)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "N", N, DM4D_DC_MAX_ROWS)) return DM4D_ERR_INVALID;
     if (B < 0 || B > DM4D_DC_MAX_VIEWS) { set_error("%s: B = %d views is outside [0, %d]", fn, B, DM4D_DC_MAX_VIEWS); return DM4D_ERR_INVALID; }
     if (N == 0 || B == 0) return DM4D_OK;
-    DC_NULL(!grad2d || !radii || !accum || !denom || !max_radii)
-    hipLaunchKernelGGL(k_dc_stats, dim3(dc_blocks(N)), dim3(kDcThreads), 0, (hipStream_t)stream, (int)B, N, (const float *)grad2d,
+    DM4D_REFUSE_NULL(!grad2d || !radii || !accum || !denom || !max_radii)
+    hipLaunchKernelGGL(k_dc_stats, dim3(blocks(N, kDcThreads)), dim3(kDcThreads), 0, (hipStream_t)stream, (int)B, N, (const float *)grad2d,
                        (const int32_t *)radii, (float *)accum, (float *)denom, (float *)max_radii);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
@@ -382,12 +368,12 @@ int dm4d_dc_classify_densify(int64_t N, const void *accum, const void *denom, co
                              float split_thresh, int32_t sphere, void *kind, void *stream)
 {
     const char *fn = "dm4d_dc_classify_densify";
-    if (dc_bad_rows(fn, "N", N, DM4D_DC_MAX_ROWS)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "N", N, DM4D_DC_MAX_ROWS)) return DM4D_ERR_INVALID;
     if (!(grad_threshold > 0.0f)) { set_error("%s: grad_threshold = %g must be > 0", fn, (double)grad_threshold); return DM4D_ERR_INVALID; }
     if (!(split_thresh == split_thresh)) { set_error("%s: split_thresh is not a number", fn); return DM4D_ERR_INVALID; }
     if (N == 0) return DM4D_OK;
-    DC_NULL(!accum || !denom || !scaling || !kind)
-    hipLaunchKernelGGL(k_dc_classify_densify, dim3(dc_blocks(N)), dim3(kDcThreads), 0, (hipStream_t)stream, N, (const float *)accum,
+    DM4D_REFUSE_NULL(!accum || !denom || !scaling || !kind)
+    hipLaunchKernelGGL(k_dc_classify_densify, dim3(blocks(N, kDcThreads)), dim3(kDcThreads), 0, (hipStream_t)stream, N, (const float *)accum,
                        (const float *)denom, (const float *)scaling, grad_threshold, split_thresh, (int)sphere, (uint8_t *)kind);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
@@ -397,11 +383,11 @@ int dm4d_dc_classify_prune(int64_t N, const void *opacity, float min_opacity, co
                            void *kind, void *stream)
 {
     const char *fn = "dm4d_dc_classify_prune";
-    if (dc_bad_rows(fn, "N", N, DM4D_DC_MAX_ROWS)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "N", N, DM4D_DC_MAX_ROWS)) return DM4D_ERR_INVALID;
     if (!(min_opacity == min_opacity)) { set_error("%s: min_opacity is not a number", fn); return DM4D_ERR_INVALID; }
     if (N == 0) return DM4D_OK;
-    DC_NULL(!opacity || !kind || (radius_limit && !max_radii))
-    hipLaunchKernelGGL(k_dc_classify_prune, dim3(dc_blocks(N)), dim3(kDcThreads), 0, (hipStream_t)stream, N, (const float *)opacity,
+    DM4D_REFUSE_NULL(!opacity || !kind || (radius_limit && !max_radii))
+    hipLaunchKernelGGL(k_dc_classify_prune, dim3(blocks(N, kDcThreads)), dim3(kDcThreads), 0, (hipStream_t)stream, N, (const float *)opacity,
                        min_opacity, (const float *)max_radii, (const float *)radius_limit, (uint8_t *)kind);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
@@ -409,7 +395,7 @@ int dm4d_dc_classify_prune(int64_t N, const void *opacity, float min_opacity, co
 
 int64_t dm4d_dc_plan_scratch_bytes(int64_t N)
 {
-    if (dc_bad_rows("dm4d_dc_plan_scratch_bytes", "N", N, DM4D_DC_MAX_ROWS)) return DM4D_ERR_INVALID;
+    if (bad_count("dm4d_dc_plan_scratch_bytes", "N", N, DM4D_DC_MAX_ROWS)) return DM4D_ERR_INVALID;
     const int64_t G = dc_tiles(N);
     return (G > 0 ? G : 1) * (int64_t)sizeof(uint4);
 }
@@ -417,17 +403,14 @@ int64_t dm4d_dc_plan_scratch_bytes(int64_t N)
 int dm4d_dc_plan_count(int64_t N, const void *kind, void *scratch, int64_t scratch_bytes, void *totals, void *stream)
 {
     const char *fn = "dm4d_dc_plan_count";
-    if (dc_bad_rows(fn, "N", N, DM4D_DC_MAX_ROWS)) return DM4D_ERR_INVALID;
-    DC_NULL(!totals || !scratch || (N > 0 && !kind))
-    if (scratch_bytes < dm4d_dc_plan_scratch_bytes(N)) {
-        set_error("%s: scratch of %lld bytes, %lld needed", fn, (long long)scratch_bytes, (long long)dm4d_dc_plan_scratch_bytes(N));
-        return DM4D_ERR_CAPACITY;
-    }
-    if (!dc_aligned16(scratch) || (reinterpret_cast<uintptr_t>(totals) & 7u)) { set_error("%s: scratch must be 16-byte, totals 8-byte aligned", fn); return DM4D_ERR_INVALID; }
+    if (bad_count(fn, "N", N, DM4D_DC_MAX_ROWS)) return DM4D_ERR_INVALID;
+    DM4D_REFUSE_NULL(!totals || !scratch || (N > 0 && !kind))
+    if (short_scratch(fn, scratch_bytes, dm4d_dc_plan_scratch_bytes(N))) return DM4D_ERR_CAPACITY;
+    if (misaligned(scratch, 16) || misaligned(totals, 8)) { set_error("%s: scratch must be 16-byte, totals 8-byte aligned", fn); return DM4D_ERR_INVALID; }
     const int G = (int)dc_tiles(N);                          // <= 65536
     if (G > 0)
         hipLaunchKernelGGL(k_dc_count, dim3((unsigned)G), dim3(kDcThreads), 0, (hipStream_t)stream, N, (const uint8_t *)kind,
-                           dc_aligned16(kind), (uint4 *)scratch);
+                           !misaligned(kind, 16), (uint4 *)scratch);
     const int chunk = (G + kDcScanThreads - 1) / kDcScanThreads;
     hipLaunchKernelGGL(k_dc_scan_totals, dim3(1), dim3(kDcScanThreads), 0, (hipStream_t)stream, N, G, chunk, (uint4 *)scratch,
                        (int64_t *)totals);
@@ -439,20 +422,17 @@ int dm4d_dc_plan_rows(int64_t N, const void *kind, int32_t S, const void *scratc
                       void *src, void *role, void *stream)
 {
     const char *fn = "dm4d_dc_plan_rows";
-    if (dc_bad_rows(fn, "N", N, DM4D_DC_MAX_ROWS) || dc_bad_children(fn, S)) return DM4D_ERR_INVALID;
-    if (dc_bad_rows(fn, "M", M, N * (int64_t)(S > 2 ? S : 2))) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "N", N, DM4D_DC_MAX_ROWS) || dc_bad_children(fn, S)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "M", M, N * (int64_t)(S > 2 ? S : 2))) return DM4D_ERR_INVALID;
     if (N == 0 || M == 0) return DM4D_OK;
-    DC_NULL(!kind || !scratch || !totals || !src || !role)
-    if (scratch_bytes < dm4d_dc_plan_scratch_bytes(N)) {
-        set_error("%s: scratch of %lld bytes, %lld needed", fn, (long long)scratch_bytes, (long long)dm4d_dc_plan_scratch_bytes(N));
-        return DM4D_ERR_CAPACITY;
-    }
-    if (!dc_aligned16(scratch) || (reinterpret_cast<uintptr_t>(totals) & 7u) || (reinterpret_cast<uintptr_t>(src) & 3u)) {
+    DM4D_REFUSE_NULL(!kind || !scratch || !totals || !src || !role)
+    if (short_scratch(fn, scratch_bytes, dm4d_dc_plan_scratch_bytes(N))) return DM4D_ERR_CAPACITY;
+    if (misaligned(scratch, 16) || misaligned(totals, 8) || misaligned(src, 4)) {
         set_error("%s: scratch must be 16-byte, totals 8-byte, src 4-byte aligned", fn);
         return DM4D_ERR_INVALID;
     }
     hipLaunchKernelGGL(k_dc_plan_rows, dim3((unsigned)dc_tiles(N)), dim3(kDcThreads), 0, (hipStream_t)stream, N, (const uint8_t *)kind,
-                       dc_aligned16(kind), (int)S, (const uint4 *)scratch, (const int64_t *)totals, M, (int32_t *)src, (uint8_t *)role);
+                       !misaligned(kind, 16), (int)S, (const uint4 *)scratch, (const int64_t *)totals, M, (int32_t *)src, (uint8_t *)role);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
 }
@@ -460,8 +440,8 @@ int dm4d_dc_plan_rows(int64_t N, const void *kind, int32_t S, const void *scratc
 int dm4d_dc_move(int64_t N, int64_t M, const void *src, const void *role, const dm4d_dc_arrays *arrays, void *stream)
 {
     const char *fn = "dm4d_dc_move";
-    if (dc_bad_rows(fn, "N", N, DM4D_DC_MAX_ROWS) || dc_bad_rows(fn, "M", M, N * (int64_t)DM4D_DC_MAX_CHILDREN)) return DM4D_ERR_INVALID;
-    DC_NULL(!arrays)
+    if (bad_count(fn, "N", N, DM4D_DC_MAX_ROWS) || bad_count(fn, "M", M, N * (int64_t)DM4D_DC_MAX_CHILDREN)) return DM4D_ERR_INVALID;
+    DM4D_REFUSE_NULL(!arrays)
     if (arrays->count < 0 || arrays->count > DM4D_DC_MAX_ARRAYS) {
         set_error("%s: %d arrays, the table holds %d", fn, arrays->count, DM4D_DC_MAX_ARRAYS);
         return DM4D_ERR_INVALID;
@@ -474,8 +454,8 @@ int dm4d_dc_move(int64_t N, int64_t M, const void *src, const void *role, const 
         if (w <= 0 || w > (1 << 20)) { set_error("%s: array %d has row width %d (must lie in [1, %d])", fn, a, w, 1 << 20); return DM4D_ERR_INVALID; }
         if (arrays->flags[a] & ~(DM4D_DC_ZERO_NEW | DM4D_DC_SKIP_CHILDREN)) { set_error("%s: array %d has unknown flags %d", fn, a, arrays->flags[a]); return DM4D_ERR_INVALID; }
         if (M > 0 && (!arrays->in[a] || !arrays->out[a])) { set_error("%s: array %d has a null pointer", fn, a); return DM4D_ERR_INVALID; }
-        if ((reinterpret_cast<uintptr_t>(arrays->in[a]) | reinterpret_cast<uintptr_t>(arrays->out[a])) & 3u) { set_error("%s: array %d is not 4-byte aligned", fn, a); return DM4D_ERR_INVALID; }
-        const bool vec = w % 4 == 0 && dc_aligned16(arrays->in[a]) && dc_aligned16(arrays->out[a]);
+        if (misaligned(arrays->in[a], 4) || misaligned(arrays->out[a], 4)) { set_error("%s: array %d is not 4-byte aligned", fn, a); return DM4D_ERR_INVALID; }
+        const bool vec = w % 4 == 0 && !misaligned(arrays->in[a], 16) && !misaligned(arrays->out[a], 16);
         T.in[a] = (const uint32_t *)arrays->in[a];
         T.out[a] = (uint32_t *)arrays->out[a];
         T.vec[a] = vec;
@@ -491,7 +471,7 @@ int dm4d_dc_move(int64_t N, int64_t M, const void *src, const void *role, const 
         return DM4D_ERR_UNSUPPORTED;
     }
     if (M == 0 || arrays->count == 0) return DM4D_OK;
-    DC_NULL(!src || !role)
+    DM4D_REFUSE_NULL(!src || !role)
     hipLaunchKernelGGL(k_dc_move, dim3((unsigned)tiles), dim3(kDcThreads), 0, (hipStream_t)stream, T, M, (const int32_t *)src,
                        (const uint8_t *)role);
     DM4D_HIP_CHECK(hipGetLastError());
@@ -503,11 +483,11 @@ int dm4d_dc_split_children(int64_t N, int64_t M, int64_t first_child, int32_t S,
                            void *scaling_out, void *stream)
 {
     const char *fn = "dm4d_dc_split_children";
-    if (dc_bad_rows(fn, "N", N, DM4D_DC_MAX_ROWS) || dc_bad_children(fn, S)) return DM4D_ERR_INVALID;
-    if (dc_bad_rows(fn, "M", M, N * (int64_t)DM4D_DC_MAX_CHILDREN) || dc_bad_rows(fn, "first_child", first_child, M)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "N", N, DM4D_DC_MAX_ROWS) || dc_bad_children(fn, S)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "M", M, N * (int64_t)DM4D_DC_MAX_CHILDREN) || bad_count(fn, "first_child", first_child, M)) return DM4D_ERR_INVALID;
     if (first_child == M) return DM4D_OK;
-    DC_NULL(!src || !role || !xyz_in || !scaling_in || !rotation_in || !noise || !xyz_out || !scaling_out)
-    hipLaunchKernelGGL(k_dc_split_children, dim3(dc_blocks(M - first_child)), dim3(kDcThreads), 0, (hipStream_t)stream, N, M, first_child,
+    DM4D_REFUSE_NULL(!src || !role || !xyz_in || !scaling_in || !rotation_in || !noise || !xyz_out || !scaling_out)
+    hipLaunchKernelGGL(k_dc_split_children, dim3(blocks(M - first_child, kDcThreads)), dim3(kDcThreads), 0, (hipStream_t)stream, N, M, first_child,
                        (int)S, (int)sphere, (const int32_t *)src, (const uint8_t *)role, (const float *)xyz_in, (const float *)scaling_in,
                        (const float *)rotation_in, (const float *)noise, (float *)xyz_out, (float *)scaling_out);
     DM4D_HIP_CHECK(hipGetLastError());
@@ -517,10 +497,10 @@ int dm4d_dc_split_children(int64_t N, int64_t M, int64_t first_child, int32_t S,
 int dm4d_dc_reset_opacity(int64_t N, void *opacity, void *exp_avg, void *exp_avg_sq, void *stream)
 {
     const char *fn = "dm4d_dc_reset_opacity";
-    if (dc_bad_rows(fn, "N", N, DM4D_DC_MAX_ROWS)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "N", N, DM4D_DC_MAX_ROWS)) return DM4D_ERR_INVALID;
     if (N == 0) return DM4D_OK;
-    DC_NULL(!opacity)
-    hipLaunchKernelGGL(k_dc_reset_opacity, dim3(dc_blocks(N)), dim3(kDcThreads), 0, (hipStream_t)stream, N, (float *)opacity,
+    DM4D_REFUSE_NULL(!opacity)
+    hipLaunchKernelGGL(k_dc_reset_opacity, dim3(blocks(N, kDcThreads)), dim3(kDcThreads), 0, (hipStream_t)stream, N, (float *)opacity,
                        (float *)exp_avg, (float *)exp_avg_sq);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;

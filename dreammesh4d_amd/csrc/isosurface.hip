@@ -19,6 +19,7 @@
 //   k_mc_classify / k_mc_vertices / k_mc_faces   marching cubes: case, triangle and vertex counts per voxel; one vertex per
 //                           crossed edge owned by the voxel, recorded in a dense edge -> vertex table; faces through that table.
 #include "common.h"
+#include "hostcheck.h"
 #include "mc_table.h"
 #include "../../include/dm4d.h"
 #include "../../include/dm4d_isosurface.h"
@@ -286,15 +287,6 @@ static bool iso_bad_grid(const char *fn, int32_t R0, int32_t R1, int32_t R2)
     return true;
 }
 
-static bool iso_bad_count(const char *fn, const char *what, int64_t n, int64_t most)
-{
-    if (n >= 0 && n <= most) return false;
-    set_error("%s: %s = %lld is outside [0, %lld]", fn, what, (long long)n, (long long)most);
-    return true;
-}
-
-static unsigned iso_blocks(int64_t n) { return (unsigned)((n + kIsoThreads - 1) / kIsoThreads); }
-
 }  // namespace dm4d
 
 using namespace dm4d;
@@ -307,11 +299,11 @@ int dm4d_iso_gaussian_records(int64_t N, const void *xyzn, const void *stdn, con
                               int32_t num_blocks, const void *vmin, const void *vmax, void *records, void *box, void *count, void *stream)
 {
     const char *fn = "dm4d_iso_gaussian_records";
-    if (iso_bad_count(fn, "N", N, INT32_MAX)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "N", N)) return DM4D_ERR_INVALID;
     if (num_blocks < 1 || num_blocks > DM4D_ISO_MAX_RESOLUTION) { set_error("%s: num_blocks = %d is outside [1, %d]", fn, num_blocks, DM4D_ISO_MAX_RESOLUTION); return DM4D_ERR_INVALID; }
     if (N == 0) return DM4D_OK;
-    if (!xyzn || !stdn || !rotation || !opacity || !vmin || !vmax || !records || !box || !count) { set_error("%s: null argument", fn); return DM4D_ERR_INVALID; }
-    hipLaunchKernelGGL(k_iso_gaussian_records, dim3(iso_blocks(N)), dim3(kIsoThreads), 0, (hipStream_t)stream, N, (const float *)xyzn,
+    DM4D_REFUSE_NULL(!xyzn || !stdn || !rotation || !opacity || !vmin || !vmax || !records || !box || !count)
+    hipLaunchKernelGGL(k_iso_gaussian_records, dim3(blocks(N, kIsoThreads)), dim3(kIsoThreads), 0, (hipStream_t)stream, N, (const float *)xyzn,
                        (const float *)stdn, (const float *)rotation, (const float *)opacity, (const float *)rgb, (int)num_blocks,
                        (const float *)vmin, (const float *)vmax, (float *)records, (int32_t *)box, (int64_t *)count);
     DM4D_HIP_CHECK(hipGetLastError());
@@ -321,11 +313,11 @@ int dm4d_iso_gaussian_records(int64_t N, const void *xyzn, const void *stdn, con
 int dm4d_iso_pair_keys(int64_t N, int64_t P, int32_t num_blocks, const void *box, const void *offset, void *keys, void *stream)
 {
     const char *fn = "dm4d_iso_pair_keys";
-    if (iso_bad_count(fn, "N", N, INT32_MAX) || iso_bad_count(fn, "P", P, INT64_MAX / 2)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "N", N) || bad_count(fn, "P", P, INT64_MAX / 2)) return DM4D_ERR_INVALID;
     if (num_blocks < 1 || num_blocks > DM4D_ISO_MAX_RESOLUTION) { set_error("%s: num_blocks = %d is outside [1, %d]", fn, num_blocks, DM4D_ISO_MAX_RESOLUTION); return DM4D_ERR_INVALID; }
     if (N == 0 || P == 0) return DM4D_OK;
-    if (!box || !offset || !keys) { set_error("%s: null argument", fn); return DM4D_ERR_INVALID; }
-    hipLaunchKernelGGL(k_iso_pair_keys, dim3(iso_blocks(N)), dim3(kIsoThreads), 0, (hipStream_t)stream, N, P, (int)num_blocks,
+    DM4D_REFUSE_NULL(!box || !offset || !keys)
+    hipLaunchKernelGGL(k_iso_pair_keys, dim3(blocks(N, kIsoThreads)), dim3(kIsoThreads), 0, (hipStream_t)stream, N, P, (int)num_blocks,
                        (const int32_t *)box, (const int64_t *)offset, (int64_t *)keys);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
@@ -335,12 +327,12 @@ int dm4d_iso_density_field(int64_t N, int64_t P, int32_t R, int32_t num_blocks, 
                            const void *block_start, void *occ, void *csum, void *stream)
 {
     const char *fn = "dm4d_iso_density_field";
-    if (iso_bad_count(fn, "N", N, INT32_MAX) || iso_bad_count(fn, "P", P, INT64_MAX / 2)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "N", N) || bad_count(fn, "P", P, INT64_MAX / 2)) return DM4D_ERR_INVALID;
     if (R < 2 || R > DM4D_ISO_MAX_RESOLUTION || num_blocks < 1 || R % num_blocks != 0) {
         set_error("%s: resolution %d must lie in [2, %d] and be a multiple of num_blocks = %d", fn, R, DM4D_ISO_MAX_RESOLUTION, num_blocks);
         return DM4D_ERR_INVALID;
     }
-    if (!coords || !block_start || !occ || (P > 0 && (!records || !keys))) { set_error("%s: null argument", fn); return DM4D_ERR_INVALID; }
+    DM4D_REFUSE_NULL(!coords || !block_start || !occ || (P > 0 && (!records || !keys)))
     const int s = R / num_blocks;
     const int chunks = (s * s * s + kIsoChunk - 1) / kIsoChunk;
     const int64_t grid = (int64_t)num_blocks * num_blocks * num_blocks * chunks;      // <= R^3 <= 2^27
@@ -362,8 +354,8 @@ int dm4d_iso_mc_classify(int32_t R0, int32_t R1, int32_t R2, const void *f, doub
     const char *fn = "dm4d_iso_mc_classify";
     if (iso_bad_grid(fn, R0, R1, R2)) return DM4D_ERR_INVALID;
     if (!(threshold == threshold)) { set_error("%s: the threshold is not a number", fn); return DM4D_ERR_INVALID; }
-    if (!f || !code || !n_tris || !n_verts) { set_error("%s: null argument", fn); return DM4D_ERR_INVALID; }
-    hipLaunchKernelGGL(k_mc_classify, dim3(iso_blocks((int64_t)R0 * R1 * R2)), dim3(kIsoThreads), 0, (hipStream_t)stream, (int)R0, (int)R1, (int)R2,
+    DM4D_REFUSE_NULL(!f || !code || !n_tris || !n_verts)
+    hipLaunchKernelGGL(k_mc_classify, dim3(blocks((int64_t)R0 * R1 * R2, kIsoThreads)), dim3(kIsoThreads), 0, (hipStream_t)stream, (int)R0, (int)R1, (int)R2,
                        (const float *)f, threshold, (int32_t *)code, (int32_t *)n_tris, (int32_t *)n_verts);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
@@ -373,11 +365,11 @@ int dm4d_iso_mc_vertices(int32_t R0, int32_t R1, int32_t R2, const void *f, cons
                          const void *vert_start, int64_t V, void *verts, void *colors, void *edge_vertex, void *stream)
 {
     const char *fn = "dm4d_iso_mc_vertices";
-    if (iso_bad_grid(fn, R0, R1, R2) || iso_bad_count(fn, "V", V, INT32_MAX)) return DM4D_ERR_INVALID;
+    if (iso_bad_grid(fn, R0, R1, R2) || bad_count(fn, "V", V)) return DM4D_ERR_INVALID;
     if (V == 0) return DM4D_OK;                      // nothing to write: an empty colour array has no address
     if ((csum != nullptr) != (colors != nullptr)) { set_error("%s: csum and colors go together", fn); return DM4D_ERR_INVALID; }
-    if (!f || !code || !vert_start || !verts || !edge_vertex) { set_error("%s: null argument", fn); return DM4D_ERR_INVALID; }
-    const dim3 grid(iso_blocks((int64_t)R0 * R1 * R2)), block(kIsoThreads);
+    DM4D_REFUSE_NULL(!f || !code || !vert_start || !verts || !edge_vertex)
+    const dim3 grid(blocks((int64_t)R0 * R1 * R2, kIsoThreads)), block(kIsoThreads);
     if (csum)
         hipLaunchKernelGGL(k_mc_vertices<true>, grid, block, 0, (hipStream_t)stream, (int)R0, (int)R1, (int)R2, (const float *)f, (const float *)csum,
                            threshold, (const int32_t *)code, (const int64_t *)vert_start, V, (float *)verts, (float *)colors, (int32_t *)edge_vertex);
@@ -392,10 +384,10 @@ int dm4d_iso_mc_faces(int32_t R0, int32_t R1, int32_t R2, const void *code, cons
                       void *faces, void *stream)
 {
     const char *fn = "dm4d_iso_mc_faces";
-    if (iso_bad_grid(fn, R0, R1, R2) || iso_bad_count(fn, "F", F, INT64_MAX / 4)) return DM4D_ERR_INVALID;
+    if (iso_bad_grid(fn, R0, R1, R2) || bad_count(fn, "F", F, INT64_MAX / 4)) return DM4D_ERR_INVALID;
     if (F == 0) return DM4D_OK;
-    if (!code || !tri_start || !edge_vertex || !faces) { set_error("%s: null argument", fn); return DM4D_ERR_INVALID; }
-    hipLaunchKernelGGL(k_mc_faces, dim3(iso_blocks((int64_t)R0 * R1 * R2)), dim3(kIsoThreads), 0, (hipStream_t)stream, (int)R0, (int)R1, (int)R2,
+    DM4D_REFUSE_NULL(!code || !tri_start || !edge_vertex || !faces)
+    hipLaunchKernelGGL(k_mc_faces, dim3(blocks((int64_t)R0 * R1 * R2, kIsoThreads)), dim3(kIsoThreads), 0, (hipStream_t)stream, (int)R0, (int)R1, (int)R2,
                        (const int32_t *)code, (const int64_t *)tri_start, (const int32_t *)edge_vertex, F, (int64_t *)faces);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;

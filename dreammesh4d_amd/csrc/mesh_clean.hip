@@ -27,6 +27,7 @@
 // and boxes would take one atomic per face / vertex on the same few addresses.  A wave whose active lanes all name the same
 // component reduces in registers (DPP) and issues one atomic per counter; a mixed wave falls back to one atomic per lane.
 #include "common.h"
+#include "hostcheck.h"
 #include "../../include/dm4d.h"
 #include "../../include/dm4d_mesh_clean.h"
 
@@ -414,36 +415,6 @@ __global__ __launch_bounds__(kMclThreads) void k_mcl_compact_faces(const int64_t
     }
 }
 
-struct MclArg {
-    const char *name;
-    const void *p;
-    unsigned align;
-    int64_t n;          // elements behind the pointer: a null pointer is refused only when n > 0
-};
-
-// true (with the error set) for a size outside [0, INT32_MAX]
-static bool mcl_bad_count(const char *fn, const char *what, int64_t n)
-{
-    if (n >= 0 && n <= INT32_MAX) return false;
-    set_error("%s: %s = %lld is outside [0, %d]", fn, what, (long long)n, INT32_MAX);
-    return true;
-}
-
-template <size_t N>
-static bool mcl_bad_args(const char *fn, const MclArg (&args)[N])
-{
-    for (const MclArg &a : args) {
-        if (!a.p) {
-            if (a.n > 0) { set_error("%s: %s is null", fn, a.name); return true; }
-            continue;
-        }
-        if (reinterpret_cast<uintptr_t>(a.p) & (a.align - 1u)) { set_error("%s: %s is not %u-byte aligned", fn, a.name, a.align); return true; }
-    }
-    return false;
-}
-
-static inline dim3 mcl_grid(int64_t n) { return dim3((unsigned)((n + kMclThreads - 1) / kMclThreads)); }
-
 }  // namespace dm4d
 
 using namespace dm4d;
@@ -456,13 +427,13 @@ int dm4d_mcl_face_flags(int64_t F, int64_t V, const void *verts, const void *fac
                         void *stream)
 {
     const char *fn = "dm4d_mcl_face_flags";
-    if (mcl_bad_count(fn, "F", F) || mcl_bad_count(fn, "V", V)) return DM4D_ERR_INVALID;
-    const MclArg args[] = {{"verts", verts, 4, F ? V : 0}, {"faces", faces, 4, F}, {"null_face", null_face, 1, F}, {"key_hi", key_hi, 8, F},
+    if (bad_count(fn, "F", F) || bad_count(fn, "V", V)) return DM4D_ERR_INVALID;
+    const Arg args[] = {{"verts", verts, 4, F ? V : 0}, {"faces", faces, 4, F}, {"null_face", null_face, 1, F}, {"key_hi", key_hi, 8, F},
                            {"key_lo", key_lo, 8, F}, {"state", state, 8, 1}};
-    if (mcl_bad_args(fn, args)) return DM4D_ERR_INVALID;
+    if (bad_args(fn, args)) return DM4D_ERR_INVALID;
     hipLaunchKernelGGL(k_mcl_state_init, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t *)state);
     if (F > 0)
-        hipLaunchKernelGGL(k_mcl_face_flags, mcl_grid(F), dim3(kMclThreads), 0, (hipStream_t)stream, F, (uint32_t)V, (const float *)verts,
+        hipLaunchKernelGGL(k_mcl_face_flags, dim3(blocks(F, kMclThreads)), dim3(kMclThreads), 0, (hipStream_t)stream, F, (uint32_t)V, (const float *)verts,
                            (const int32_t *)faces, (uint8_t *)null_face, (int64_t *)key_hi, (int64_t *)key_lo, (uint32_t *)state);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
@@ -472,12 +443,12 @@ int dm4d_mcl_face_first(int64_t F, const void *perm, const void *key_hi, const v
                         void *stream)
 {
     const char *fn = "dm4d_mcl_face_first";
-    if (mcl_bad_count(fn, "F", F)) return DM4D_ERR_INVALID;
-    const MclArg args[] = {{"perm", perm, 8, F}, {"key_hi", key_hi, 8, F}, {"key_lo", key_lo, 8, F}, {"null_face", null_face, 1, F},
+    if (bad_count(fn, "F", F)) return DM4D_ERR_INVALID;
+    const Arg args[] = {{"perm", perm, 8, F}, {"key_hi", key_hi, 8, F}, {"key_lo", key_lo, 8, F}, {"null_face", null_face, 1, F},
                            {"alive", alive, 1, F}, {"state", state, 8, 1}};
-    if (mcl_bad_args(fn, args)) return DM4D_ERR_INVALID;
+    if (bad_args(fn, args)) return DM4D_ERR_INVALID;
     if (F == 0) return DM4D_OK;
-    hipLaunchKernelGGL(k_mcl_face_first, mcl_grid(F), dim3(kMclThreads), 0, (hipStream_t)stream, F, (const int64_t *)perm, (const int64_t *)key_hi,
+    hipLaunchKernelGGL(k_mcl_face_first, dim3(blocks(F, kMclThreads)), dim3(kMclThreads), 0, (hipStream_t)stream, F, (const int64_t *)perm, (const int64_t *)key_hi,
                        (const int64_t *)key_lo, (const uint8_t *)null_face, (uint8_t *)alive, (uint32_t *)state);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
@@ -486,16 +457,16 @@ int dm4d_mcl_face_first(int64_t F, const void *perm, const void *key_hi, const v
 int dm4d_mcl_components_round(int64_t F, int64_t V, const void *faces, const void *alive, int32_t first_round, void *parent, void *stream)
 {
     const char *fn = "dm4d_mcl_components_round";
-    if (mcl_bad_count(fn, "F", F) || mcl_bad_count(fn, "V", V)) return DM4D_ERR_INVALID;
-    const MclArg args[] = {{"faces", faces, 4, F}, {"alive", alive, 1, 0}, {"parent", parent, 4, V}};
-    if (mcl_bad_args(fn, args)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "F", F) || bad_count(fn, "V", V)) return DM4D_ERR_INVALID;
+    const Arg args[] = {{"faces", faces, 4, F}, {"alive", alive, 1, 0}, {"parent", parent, 4, V}};
+    if (bad_args(fn, args)) return DM4D_ERR_INVALID;
     if (V == 0) return DM4D_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (first_round) hipLaunchKernelGGL(k_mcl_init_parent, mcl_grid(V), dim3(kMclThreads), 0, st, V, (int32_t *)parent);
+    if (first_round) hipLaunchKernelGGL(k_mcl_init_parent, dim3(blocks(V, kMclThreads)), dim3(kMclThreads), 0, st, V, (int32_t *)parent);
     if (F > 0) {
-        hipLaunchKernelGGL(k_mcl_hook, mcl_grid(F), dim3(kMclThreads), 0, st, F, (uint32_t)V, (const int32_t *)faces, (const uint8_t *)alive,
+        hipLaunchKernelGGL(k_mcl_hook, dim3(blocks(F, kMclThreads)), dim3(kMclThreads), 0, st, F, (uint32_t)V, (const int32_t *)faces, (const uint8_t *)alive,
                            (int32_t *)parent);
-        hipLaunchKernelGGL(k_mcl_flatten, mcl_grid(V), dim3(kMclThreads), 0, st, V, (int32_t *)parent);
+        hipLaunchKernelGGL(k_mcl_flatten, dim3(blocks(V, kMclThreads)), dim3(kMclThreads), 0, st, V, (int32_t *)parent);
     }
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
@@ -505,21 +476,21 @@ int dm4d_mcl_component_stats(int64_t F, int64_t V, const void *verts, const void
                              void *box, void *state, void *stream)
 {
     const char *fn = "dm4d_mcl_component_stats";
-    if (mcl_bad_count(fn, "F", F) || mcl_bad_count(fn, "V", V)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "F", F) || bad_count(fn, "V", V)) return DM4D_ERR_INVALID;
     if ((verts != nullptr) != (box != nullptr) && V > 0) { set_error("%s: verts and box go together", fn); return DM4D_ERR_INVALID; }
-    const MclArg args[] = {{"verts", verts, 4, 0}, {"faces", faces, 4, F}, {"alive", alive, 1, 0}, {"labels", labels, 4, V},
+    const Arg args[] = {{"verts", verts, 4, 0}, {"faces", faces, 4, F}, {"alive", alive, 1, 0}, {"labels", labels, 4, V},
                            {"face_count", face_count, 4, V}, {"box", box, 4, 0}, {"state", state, 8, 1}};
-    if (mcl_bad_args(fn, args)) return DM4D_ERR_INVALID;
+    if (bad_args(fn, args)) return DM4D_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_mcl_round_reset, dim3(1), dim3(64), 0, st, (uint32_t *)state);
     if (V > 0) {
-        hipLaunchKernelGGL(k_mcl_stats_init, mcl_grid(V), dim3(kMclThreads), 0, st, V, (const int32_t *)labels, (int32_t *)face_count,
+        hipLaunchKernelGGL(k_mcl_stats_init, dim3(blocks(V, kMclThreads)), dim3(kMclThreads), 0, st, V, (const int32_t *)labels, (int32_t *)face_count,
                            (uint32_t *)box, (uint32_t *)state);
         if (box)
-            hipLaunchKernelGGL(k_mcl_stats_vertices, mcl_grid(V), dim3(kMclThreads), 0, st, V, (const float *)verts, (const int32_t *)labels,
+            hipLaunchKernelGGL(k_mcl_stats_vertices, dim3(blocks(V, kMclThreads)), dim3(kMclThreads), 0, st, V, (const float *)verts, (const int32_t *)labels,
                                (uint32_t *)box);
         if (F > 0)
-            hipLaunchKernelGGL(k_mcl_stats_faces, mcl_grid(F), dim3(kMclThreads), 0, st, F, (uint32_t)V, (const int32_t *)faces,
+            hipLaunchKernelGGL(k_mcl_stats_faces, dim3(blocks(F, kMclThreads)), dim3(kMclThreads), 0, st, F, (uint32_t)V, (const int32_t *)faces,
                                (const uint8_t *)alive, (const int32_t *)labels, (int32_t *)face_count, (uint32_t *)state);
     }
     DM4D_HIP_CHECK(hipGetLastError());
@@ -531,21 +502,21 @@ int dm4d_mcl_keep(int64_t F, int64_t V, const void *faces, const void *alive, co
                   void *stream)
 {
     const char *fn = "dm4d_mcl_keep";
-    if (mcl_bad_count(fn, "F", F) || mcl_bad_count(fn, "V", V) || mcl_bad_count(fn, "min_f", min_f)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "F", F) || bad_count(fn, "V", V) || bad_count(fn, "min_f", min_f)) return DM4D_ERR_INVALID;
     if (!(thr2 >= 0.0) || (use_d != 0 && use_d != 1) || (largest != 0 && largest != 1)) {
         set_error("%s: thr2 = %g must be a number >= 0, use_d = %d and largest = %d flags 0 or 1", fn, thr2, use_d, largest);
         return DM4D_ERR_INVALID;
     }
-    const MclArg args[] = {{"faces", faces, 4, V ? F : 0}, {"alive", alive, 1, V ? F : 0}, {"labels", labels, 4, V}, {"face_count", face_count, 4, V},
+    const Arg args[] = {{"faces", faces, 4, V ? F : 0}, {"alive", alive, 1, V ? F : 0}, {"labels", labels, 4, V}, {"face_count", face_count, 4, V},
                            {"box", box, 4, use_d ? V : 0}, {"comp_keep", comp_keep, 1, V}, {"keep_vertex", keep_vertex, 1, V},
                            {"keep_face", keep_face, 1, V ? F : 0}, {"state", state, 8, 1}};
-    if (mcl_bad_args(fn, args)) return DM4D_ERR_INVALID;
+    if (bad_args(fn, args)) return DM4D_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_mcl_keep_reset, dim3(1), dim3(64), 0, st, (uint32_t *)state);
     if (V > 0) {
-        hipLaunchKernelGGL(k_mcl_comp_keep, mcl_grid(V), dim3(kMclThreads), 0, st, V, (const int32_t *)labels, (const int32_t *)face_count,
+        hipLaunchKernelGGL(k_mcl_comp_keep, dim3(blocks(V, kMclThreads)), dim3(kMclThreads), 0, st, V, (const int32_t *)labels, (const int32_t *)face_count,
                            (const uint32_t *)box, thr2, (int)use_d, min_f, (int)largest, (uint8_t *)comp_keep, (uint32_t *)state);
-        hipLaunchKernelGGL(k_mcl_keep_masks, mcl_grid(V > F ? V : F), dim3(kMclThreads), 0, st, F, V, (const int32_t *)faces, (const uint8_t *)alive,
+        hipLaunchKernelGGL(k_mcl_keep_masks, dim3(blocks(V > F ? V : F, kMclThreads)), dim3(kMclThreads), 0, st, F, V, (const int32_t *)faces, (const uint8_t *)alive,
                            (const int32_t *)labels, (const uint8_t *)comp_keep, (int)largest, (const uint32_t *)state, (uint8_t *)keep_vertex,
                            (uint8_t *)keep_face);
     }
@@ -558,21 +529,21 @@ int dm4d_mcl_compact(int64_t F, int64_t V, int64_t Fo, int64_t Vo, const void *v
                      void *vertex_map, void *face_map, void *stream)
 {
     const char *fn = "dm4d_mcl_compact";
-    if (mcl_bad_count(fn, "F", F) || mcl_bad_count(fn, "V", V) || mcl_bad_count(fn, "Fo", Fo) || mcl_bad_count(fn, "Vo", Vo)) return DM4D_ERR_INVALID;
+    if (bad_count(fn, "F", F) || bad_count(fn, "V", V) || bad_count(fn, "Fo", Fo) || bad_count(fn, "Vo", Vo)) return DM4D_ERR_INVALID;
     if (Fo > F || Vo > V) { set_error("%s: Fo = %lld of F = %lld faces, Vo = %lld of V = %lld vertices", fn, (long long)Fo, (long long)F, (long long)Vo, (long long)V); return DM4D_ERR_INVALID; }
     if ((colors != nullptr) != (out_colors != nullptr) && Vo > 0) { set_error("%s: colors and out_colors go together", fn); return DM4D_ERR_INVALID; }
-    const MclArg args[] = {{"verts", verts, 4, V}, {"colors", colors, 4, 0}, {"faces", faces, 4, V ? F : 0}, {"keep_vertex", keep_vertex, 1, V},
+    const Arg args[] = {{"verts", verts, 4, V}, {"colors", colors, 4, 0}, {"faces", faces, 4, V ? F : 0}, {"keep_vertex", keep_vertex, 1, V},
                            {"vert_end", vert_end, 8, V}, {"keep_face", keep_face, 1, V ? F : 0}, {"face_end", face_end, 8, V ? F : 0},
                            {"out_verts", out_verts, 4, Vo}, {"out_colors", out_colors, 4, 0}, {"out_faces", out_faces, 8, Fo},
                            {"vertex_map", vertex_map, 8, V}, {"face_map", face_map, 8, Fo}};
-    if (mcl_bad_args(fn, args)) return DM4D_ERR_INVALID;
+    if (bad_args(fn, args)) return DM4D_ERR_INVALID;
     if (V == 0) return DM4D_OK;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_mcl_compact_vertices, mcl_grid(V), dim3(kMclThreads), 0, st, V, Vo, (const float *)verts,
+    hipLaunchKernelGGL(k_mcl_compact_vertices, dim3(blocks(V, kMclThreads)), dim3(kMclThreads), 0, st, V, Vo, (const float *)verts,
                        Vo > 0 ? (const float *)colors : nullptr, (const uint8_t *)keep_vertex, (const int64_t *)vert_end, (float *)out_verts,
                        (float *)out_colors, (int64_t *)vertex_map);
     if (F > 0 && Fo > 0)
-        hipLaunchKernelGGL(k_mcl_compact_faces, mcl_grid(F), dim3(kMclThreads), 0, st, F, V, Fo, Vo, (const int32_t *)faces,
+        hipLaunchKernelGGL(k_mcl_compact_faces, dim3(blocks(F, kMclThreads)), dim3(kMclThreads), 0, st, F, V, Fo, Vo, (const int32_t *)faces,
                            (const uint8_t *)keep_vertex, (const int64_t *)vert_end, (const uint8_t *)keep_face, (const int64_t *)face_end,
                            (int64_t *)out_faces, (int64_t *)face_map);
     DM4D_HIP_CHECK(hipGetLastError());

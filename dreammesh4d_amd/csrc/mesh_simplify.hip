@@ -21,6 +21,7 @@
 // members at once (order[] is read coalesced), parks them in LDS, and the lanes 0..NC-1 add their component of the members in
 // index order -- NC independent serial chains, one ds_read_b32 + cvt + v_add_f64 per member, the reads independent of the sums.
 #include "common.h"
+#include "hostcheck.h"
 #include "../../include/dm4d.h"
 
 namespace dm4d {
@@ -156,14 +157,6 @@ __global__ __launch_bounds__(kSimThreads) void k_simplify_face_first(const int64
     keep[f] = (a >= 0 && first) ? 1 : 0;
 }
 
-// true (with the error set) unless 0 <= n <= INT32_MAX
-static bool bad_count(const char *fn, const char *what, int64_t n)
-{
-    if (n >= 0 && n <= INT32_MAX) return false;
-    set_error("%s: %s = %lld is outside [0, %d]", fn, what, (long long)n, INT32_MAX);
-    return true;
-}
-
 }  // namespace dm4d
 
 using namespace dm4d;
@@ -186,8 +179,8 @@ int dm4d_simplify_vertex_keys(int64_t V, const float *verts, double origin_x, do
         return DM4D_ERR_UNSUPPORTED;
     }
     if (V == 0) return DM4D_OK;
-    if (!verts || !keys) { set_error("%s: null argument", fn); return DM4D_ERR_INVALID; }
-    hipLaunchKernelGGL(k_simplify_vertex_keys, dim3((unsigned)((V + kSimThreads - 1) / kSimThreads)), dim3(kSimThreads), 0, (hipStream_t)stream,
+    DM4D_REFUSE_NULL(!verts || !keys)
+    hipLaunchKernelGGL(k_simplify_vertex_keys, dim3(blocks(V, kSimThreads)), dim3(kSimThreads), 0, (hipStream_t)stream,
                        V, verts, origin_x, origin_y, origin_z, voxel, nx, ny, keys);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
@@ -201,8 +194,8 @@ int dm4d_simplify_cluster_average(int64_t V, int64_t C, const int64_t *order, co
     if (C > V || (V > 0 && C == 0)) { set_error("%s: %lld clusters of %lld vertices", fn, (long long)C, (long long)V); return DM4D_ERR_INVALID; }
     if ((colors != nullptr) != (out_colors != nullptr)) { set_error("%s: colors and out_colors go together", fn); return DM4D_ERR_INVALID; }
     if (V == 0) return DM4D_OK;
-    if (!order || !run_start || !verts || !out_verts || !vertex_cluster) { set_error("%s: null argument", fn); return DM4D_ERR_INVALID; }
-    const dim3 grid((unsigned)((C + kSimWaves - 1) / kSimWaves)), block(kSimThreads);
+    DM4D_REFUSE_NULL(!order || !run_start || !verts || !out_verts || !vertex_cluster)
+    const dim3 grid(blocks(C, kSimWaves)), block(kSimThreads);
     if (colors)
         hipLaunchKernelGGL(k_simplify_cluster_average<6>, grid, block, 0, (hipStream_t)stream, V, C, order, run_start, verts, colors, out_verts,
                            out_colors, vertex_cluster);
@@ -220,8 +213,8 @@ int dm4d_simplify_face_remap(int64_t F, int64_t V, int64_t C, const int64_t *fac
     if (bad_count(fn, "F", F) || bad_count(fn, "V", V) || bad_count(fn, "C", C)) return DM4D_ERR_INVALID;
     if (C > V) { set_error("%s: %lld clusters of %lld vertices", fn, (long long)C, (long long)V); return DM4D_ERR_INVALID; }
     if (F == 0) return DM4D_OK;
-    if (!faces || !vertex_cluster || !canon || !key_bc) { set_error("%s: null argument", fn); return DM4D_ERR_INVALID; }
-    hipLaunchKernelGGL(k_simplify_face_remap, dim3((unsigned)((F + kSimThreads - 1) / kSimThreads)), dim3(kSimThreads), 0, (hipStream_t)stream,
+    DM4D_REFUSE_NULL(!faces || !vertex_cluster || !canon || !key_bc)
+    hipLaunchKernelGGL(k_simplify_face_remap, dim3(blocks(F, kSimThreads)), dim3(kSimThreads), 0, (hipStream_t)stream,
                        F, V, C, faces, vertex_cluster, canon, key_bc);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
@@ -232,8 +225,8 @@ int dm4d_simplify_face_first(int64_t F, const int64_t *perm, const int64_t *cano
     const char *fn = "dm4d_simplify_face_first";
     if (bad_count(fn, "F", F)) return DM4D_ERR_INVALID;
     if (F == 0) return DM4D_OK;
-    if (!perm || !canon || !keep) { set_error("%s: null argument", fn); return DM4D_ERR_INVALID; }
-    hipLaunchKernelGGL(k_simplify_face_first, dim3((unsigned)((F + kSimThreads - 1) / kSimThreads)), dim3(kSimThreads), 0, (hipStream_t)stream,
+    DM4D_REFUSE_NULL(!perm || !canon || !keep)
+    hipLaunchKernelGGL(k_simplify_face_first, dim3(blocks(F, kSimThreads)), dim3(kSimThreads), 0, (hipStream_t)stream,
                        F, perm, canon, keep);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;

@@ -13,6 +13,7 @@
 // of the edges that point at it -- no atomics, deterministic.
 #include <mutex>
 #include "common.h"
+#include "hostcheck.h"
 #include "arap_fit.h"
 #include "../../include/dm4d.h"
 
@@ -440,7 +441,7 @@ int dm4d_arap_fit_rotations(int32_t T, int32_t V, const int32_t *csr_offsets, co
     if (T == 0 || V == 0) return DM4D_OK;
     if (!rotations_out) { set_error("arap: null output"); return DM4D_ERR_INVALID; }
     ArapAdj a{V, csr_offsets, neighbors, nullptr, weights, rest_edges};
-    hipLaunchKernelGGL(k_arap_fit, dim3((unsigned)(((size_t)V + kFitVerts - 1) / kFitVerts), T), dim3(256), 0, (hipStream_t)stream, a, xyz_prime,
+    hipLaunchKernelGGL(k_arap_fit, dim3(blocks(V, kFitVerts), T), dim3(256), 0, (hipStream_t)stream, a, xyz_prime,
                        rotations_out, flags_out);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
@@ -497,7 +498,7 @@ int dm4d_normal_consistency_backward_scratch(int32_t T, int32_t V, int32_t P, co
     if (T < 0 || V < 0 || P < 0) { set_error("normal consistency: negative size"); return DM4D_ERR_INVALID; }
     if (T == 0 || V == 0) return DM4D_OK;
     if (!pairs || !vert_offsets || !vert_items || !xyz || !g_loss || !g_xyz) { set_error("normal consistency: null tensor"); return DM4D_ERR_INVALID; }
-    if (P > 0 && (!scratch || ((uintptr_t)scratch & 15) != 0)) { set_error("normal consistency: the backward needs a 16-byte aligned scratch of T P 12 floats"); return DM4D_ERR_INVALID; }
+    if (P > 0 && (!scratch || misaligned(scratch, 16))) { set_error("normal consistency: the backward needs a 16-byte aligned scratch of T P 12 floats"); return DM4D_ERR_INVALID; }
     NcPairs pr{P > 0 ? P : 1, pairs};
     if (P > 0) {
         hipLaunchKernelGGL(k_nc_bwd_pairs, dim3((P + 255) / 256, T), dim3(256), 0, (hipStream_t)stream, pr, V, xyz, scratch);
@@ -514,7 +515,7 @@ int dm4d_quat_to_matrix_forward(int64_t n, const float *quat_xyzw, float *matric
     if (n < 0) { set_error("quat_to_matrix: negative size"); return DM4D_ERR_INVALID; }
     if (n == 0) return DM4D_OK;
     if (!quat_xyzw || !matrices) { set_error("quat_to_matrix: null tensor"); return DM4D_ERR_INVALID; }
-    if (((uintptr_t)quat_xyzw & 15) != 0) { set_error("quat_to_matrix: quaternions must be 16-byte aligned"); return DM4D_ERR_INVALID; }
+    if (misaligned(quat_xyzw, 16)) { set_error("quat_to_matrix: quaternions must be 16-byte aligned"); return DM4D_ERR_INVALID; }
     hipLaunchKernelGGL(k_quat_matrix_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (size_t)n, quat_xyzw, matrices);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
@@ -525,7 +526,7 @@ int dm4d_quat_to_matrix_backward_pypose(int64_t n, const float *matrices, const 
     if (n < 0) { set_error("quat_to_matrix: negative size"); return DM4D_ERR_INVALID; }
     if (n == 0) return DM4D_OK;
     if (!matrices || !g_matrices || !g_quat) { set_error("quat_to_matrix: null tensor"); return DM4D_ERR_INVALID; }
-    if (((uintptr_t)g_quat & 15) != 0) { set_error("quat_to_matrix: the quaternion gradient must be 16-byte aligned"); return DM4D_ERR_INVALID; }
+    if (misaligned(g_quat, 16)) { set_error("quat_to_matrix: the quaternion gradient must be 16-byte aligned"); return DM4D_ERR_INVALID; }
     hipLaunchKernelGGL(k_quat_matrix_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (size_t)n, matrices, g_matrices, g_quat);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;

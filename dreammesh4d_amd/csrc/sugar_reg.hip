@@ -18,6 +18,7 @@
 //   k_sr_gather      one lane per Gaussian j: its own chunks, then the chunks of every (g,k) that lists j in ascending
 //                    (g, k, chunk) through the reverse table, in float64; then the chain through M, m, n and R to the inputs
 #include "common.h"
+#include "hostcheck.h"
 #include "../../include/dm4d.h"
 #include "../../include/dm4d_sugar_reg.h"
 
@@ -458,10 +459,9 @@ static SrLayout sr_layout(int64_t N, int32_t K, int64_t S)
 
 static bool sr_bad_sizes(const char *fn, int64_t N, int32_t K, int64_t S)
 {
-    if (N < 0 || N > DM4D_SR_MAX_POINTS) { set_error("%s: N = %lld is outside [0, %d]", fn, (long long)N, DM4D_SR_MAX_POINTS); return true; }
+    if (bad_count(fn, "N", N, DM4D_SR_MAX_POINTS)) return true;
     if (K < 1 || K > DM4D_SR_MAX_K) { set_error("%s: K = %d is outside [1, %d]", fn, K, DM4D_SR_MAX_K); return true; }
-    if (S < 0 || S > DM4D_SR_MAX_SAMPLES) { set_error("%s: S = %lld is outside [0, %d]", fn, (long long)S, DM4D_SR_MAX_SAMPLES); return true; }
-    return false;
+    return bad_count(fn, "S", S, DM4D_SR_MAX_SAMPLES);
 }
 
 static bool sr_bad_scalars(const char *fn, float sampling_scale, float density_factor, int32_t with_normal_loss)
@@ -472,24 +472,16 @@ static bool sr_bad_scalars(const char *fn, float sampling_scale, float density_f
     return false;
 }
 
-static bool sr_bad_scratch(const char *fn, const void *scratch, int64_t scratch_bytes, const SrLayout &L)
+static bool sr_bad_scratch(const char *fn, const void *scratch)
 {
     if (!scratch) { set_error("%s: null argument", fn); return true; }
-    if (reinterpret_cast<uintptr_t>(scratch) & 15u) { set_error("%s: scratch must be 16-byte aligned", fn); return true; }
+    if (misaligned(scratch, 16)) { set_error("%s: scratch must be 16-byte aligned", fn); return true; }
     return false;
 }
-
-static unsigned sr_blocks(int64_t n) { return (unsigned)((n + kSrThreads - 1) / kSrThreads); }
 
 }  // namespace dm4d
 
 using namespace dm4d;
-
-#define SR_NULL(cond)                                   \
-    if (cond) {                                         \
-        set_error("%s: null argument", fn);             \
-        return DM4D_ERR_INVALID;                        \
-    }
 
 extern "C" {
 
@@ -509,32 +501,29 @@ int dm4d_sr_forward(int64_t N, int32_t K, int64_t S, const void *xyz, const void
     const char *fn = "dm4d_sr_forward";
     if (sr_bad_sizes(fn, N, K, S) || sr_bad_scalars(fn, sampling_scale, density_factor, with_normal_loss)) return DM4D_ERR_INVALID;
     if (N == 0 || S == 0) return DM4D_OK;
-    SR_NULL(!xyz || !scales || !quats || !opac || !knn_idx || !sample_idx || !order || !eps || !density || !beta || !density_term || !losses)
-    SR_NULL(with_normal_loss && !normal_term)
+    DM4D_REFUSE_NULL(!xyz || !scales || !quats || !opac || !knn_idx || !sample_idx || !order || !eps || !density || !beta || !density_term || !losses)
+    DM4D_REFUSE_NULL(with_normal_loss && !normal_term)
     const SrLayout L = sr_layout(N, K, S);
-    if (sr_bad_scratch(fn, scratch, scratch_bytes, L)) return DM4D_ERR_INVALID;
-    if (scratch_bytes < L.bytes) {
-        set_error("%s: scratch of %lld bytes, %lld needed", fn, (long long)scratch_bytes, (long long)L.bytes);
-        return DM4D_ERR_CAPACITY;
-    }
+    if (sr_bad_scratch(fn, scratch)) return DM4D_ERR_INVALID;
+    if (short_scratch(fn, scratch_bytes, L.bytes)) return DM4D_ERR_CAPACITY;
     hipStream_t st = (hipStream_t)stream;
     float *rec = reinterpret_cast<float *>((char *)scratch + L.rec);
     double *partial = reinterpret_cast<double *>((char *)scratch + L.partial);
-    hipLaunchKernelGGL(k_sr_prepare, dim3(sr_blocks(N)), dim3(kSrThreads), 0, st, (int)N, (const float *)xyz, (const float *)scales,
+    hipLaunchKernelGGL(k_sr_prepare, dim3(blocks(N, kSrThreads)), dim3(kSrThreads), 0, st, (int)N, (const float *)xyz, (const float *)scales,
                        (const float *)quats, (const float *)opac, rec);
     DM4D_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_sr_forward, dim3(sr_blocks(S)), dim3(kSrThreads), 0, st, (int)K, (int)S, (const float *)xyz,
+    hipLaunchKernelGGL(k_sr_forward, dim3(blocks(S, kSrThreads)), dim3(kSrThreads), 0, st, (int)K, (int)S, (const float *)xyz,
                        (const float *)scales, (const float *)quats, (const int32_t *)knn_idx, (const int32_t *)sample_idx,
                        (const int32_t *)order, (const float *)eps, sampling_scale, density_factor, (int)with_normal_loss,
                        (const float *)rec, (float *)density, (float *)beta, (float *)density_term, (float *)normal_term);
     DM4D_HIP_CHECK(hipGetLastError());
-    const int64_t want = (S + kSrThreads - 1) / kSrThreads;
-    const int blocks = (int)(want < kSrPartials ? want : kSrPartials);
-    const int per_block = (int)((S + blocks - 1) / blocks);
-    hipLaunchKernelGGL(k_sr_partial, dim3(blocks), dim3(kSrThreads), 0, st, (int)S, per_block, (const float *)density_term,
+    const int64_t want = blocks(S, kSrThreads);
+    const int n_partial = (int)(want < kSrPartials ? want : kSrPartials);
+    const int per_block = (int)((S + n_partial - 1) / n_partial);
+    hipLaunchKernelGGL(k_sr_partial, dim3(n_partial), dim3(kSrThreads), 0, st, (int)S, per_block, (const float *)density_term,
                        with_normal_loss ? (const float *)normal_term : (const float *)nullptr, partial);
     DM4D_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_sr_final, dim3(1), dim3(kSrThreads), 0, st, (int)S, blocks, (const double *)partial, (float *)losses);
+    hipLaunchKernelGGL(k_sr_final, dim3(1), dim3(kSrThreads), 0, st, (int)S, n_partial, (const double *)partial, (float *)losses);
     DM4D_HIP_CHECK(hipGetLastError());
     return DM4D_OK;
 }
@@ -548,28 +537,24 @@ int dm4d_sr_backward(int64_t N, int32_t K, int64_t S, const void *xyz, const voi
     const char *fn = "dm4d_sr_backward";
     if (sr_bad_sizes(fn, N, K, S) || sr_bad_scalars(fn, sampling_scale, density_factor, with_normal_loss)) return DM4D_ERR_INVALID;
     if (N == 0 || S == 0) return DM4D_OK;
-    SR_NULL(!xyz || !scales || !quats || !opac || !knn_idx || !sample_idx || !order || !eps || !upstream || !seg_ptr || !chunk_ptr || !rev_ptr || !rev_pos)
+    DM4D_REFUSE_NULL(!xyz || !scales || !quats || !opac || !knn_idx || !sample_idx || !order || !eps || !upstream || !seg_ptr || !chunk_ptr || !rev_ptr || !rev_pos)
     const SrLayout L = sr_layout(N, K, S);
-    if (sr_bad_scratch(fn, scratch, scratch_bytes, L)) return DM4D_ERR_INVALID;
-    if (scratch_bytes < L.bytes) {
-        set_error("%s: scratch of %lld bytes, %lld needed", fn, (long long)scratch_bytes, (long long)L.bytes);
-        return DM4D_ERR_CAPACITY;
-    }
+    if (sr_bad_scratch(fn, scratch)) return DM4D_ERR_INVALID;
+    if (short_scratch(fn, scratch_bytes, L.bytes)) return DM4D_ERR_CAPACITY;
     hipStream_t st = (hipStream_t)stream;
     float *rec = reinterpret_cast<float *>((char *)scratch + L.rec);
     float *slot = reinterpret_cast<float *>((char *)scratch + L.slot);
     float *own = reinterpret_cast<float *>((char *)scratch + L.own);
-    hipLaunchKernelGGL(k_sr_prepare, dim3(sr_blocks(N)), dim3(kSrThreads), 0, st, (int)N, (const float *)xyz, (const float *)scales,
+    hipLaunchKernelGGL(k_sr_prepare, dim3(blocks(N, kSrThreads)), dim3(kSrThreads), 0, st, (int)N, (const float *)xyz, (const float *)scales,
                        (const float *)quats, (const float *)opac, rec);
     DM4D_HIP_CHECK(hipGetLastError());
-    const int64_t rows_per_block = kSrThreads / kSrChunk;
-    hipLaunchKernelGGL(k_sr_backward, dim3((unsigned)((L.chunks + rows_per_block - 1) / rows_per_block)), dim3(kSrThreads), 0, st, (int)N,
+    hipLaunchKernelGGL(k_sr_backward, dim3(blocks(L.chunks, kSrThreads / kSrChunk)), dim3(kSrThreads), 0, st, (int)N,
                        (int)K, (int)S, (const float *)xyz, (const float *)scales, (const float *)quats, (const int32_t *)knn_idx,
                        (const int32_t *)sample_idx, (const int32_t *)order, (const float *)eps, sampling_scale, density_factor,
                        (int)with_normal_loss, (const float *)upstream, (const int32_t *)seg_ptr, (const int32_t *)chunk_ptr,
                        (const float *)rec, slot, own);
     DM4D_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_sr_gather, dim3(sr_blocks(N)), dim3(kSrThreads), 0, st, (int)N, (int)K, (const float *)scales,
+    hipLaunchKernelGGL(k_sr_gather, dim3(blocks(N, kSrThreads)), dim3(kSrThreads), 0, st, (int)N, (int)K, (const float *)scales,
                        (const float *)quats, (const int32_t *)chunk_ptr, (const int32_t *)rev_ptr, (const int32_t *)rev_pos,
                        (const float *)slot, (const float *)own, (float *)d_xyz, (float *)d_scales, (float *)d_quats, (float *)d_opac);
     DM4D_HIP_CHECK(hipGetLastError());

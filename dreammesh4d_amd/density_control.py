@@ -18,14 +18,11 @@ import ctypes
 import torch
 
 from . import _lib
+from ._args import no_cpu_path as _no_cpu_path
 
 KEEP, DROP, CLONE, SPLIT = _lib.DM4D_DC_KEEP, _lib.DM4D_DC_DROP, _lib.DM4D_DC_CLONE, _lib.DM4D_DC_SPLIT
 ROLE_KEPT, ROLE_CLONE, ROLE_CHILD = _lib.DM4D_DC_ROLE_KEPT, _lib.DM4D_DC_ROLE_CLONE, _lib.DM4D_DC_ROLE_CHILD
 MAX_ARRAYS = _lib.DM4D_DC_MAX_ARRAYS
-
-
-def _no_cpu_path(what):
-    return _lib.Dm4dError(f"{what}: tensors must live on one HIP device; there is no CPU path")
 
 
 def _device_of(what, *tensors):

@@ -28,13 +28,9 @@ import os
 import numpy as np
 import torch
 
+from ._args import no_cpu_path as _no_cpu_path
+
 OPACITY_FLOOR = 0.005
-
-
-def _no_cpu_path(what):
-    from . import _lib
-
-    return _lib.Dm4dError(f"{what}: tensors must live on one HIP device; there is no CPU path")
 
 
 def _checked_grid(resolution, num_blocks):

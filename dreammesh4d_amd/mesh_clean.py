@@ -35,29 +35,17 @@ import os
 import numpy as np
 import torch
 
+from . import _args
+
 KEEP_MODES = ("all", "largest")
 MAX_COUNT = (1 << 31) - 1
 MAX_ROUNDS = 64
 
 
-def _no_cpu_path(what):
-    from . import _lib
-
-    return _lib.Dm4dError(f"{what}: tensors must live on one HIP device; there is no CPU path")
-
-
-def _check_range(what, faces, n_verts):
-    """Face indices of the device tensor `faces` lie in [0, n_verts): one host read."""
-    lo, hi = (int(v) for v in torch.stack((faces.min(), faces.max())).cpu())
-    if lo < 0 or hi >= n_verts:
-        raise ValueError(f"{what}: face indices span [{lo}, {hi}], the mesh has {n_verts} vertices")
-
-
 def _checked_faces(what, faces):
     if not torch.is_tensor(faces):
         raise TypeError(f"{what}: faces must be a torch tensor")
-    if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"{what}: faces must be int32 / int64 [F,3] (got {faces.dtype} {tuple(faces.shape)})")
+    _args.check_face_tensor(what, faces)
     if faces.shape[0] > MAX_COUNT:
         raise ValueError(f"{what}: {faces.shape[0]} faces, more than {MAX_COUNT}")
 
@@ -102,11 +90,11 @@ def connected_components(faces, n_verts):
         raise ValueError(f"{what}: n_verts must be an integer in [0, {MAX_COUNT}] (got {n_verts!r})")
     dev = faces.device
     if dev.type != "cuda":
-        raise _no_cpu_path(what)
+        raise _args.no_cpu_path(what)
     V, F = int(n_verts), int(faces.shape[0])
     with torch.cuda.device(dev):
         if F:
-            _check_range(what, faces, V)
+            _args.check_index_range(what, _args.FACE_INDICES, faces, V)
         faces32 = faces.detach().to(torch.int32).contiguous()
         state = torch.zeros(_lib.DM4D_MCL_STATE_WORDS, dtype=torch.int32, device=dev)
         face_count = torch.empty(V, dtype=torch.int32, device=dev)
@@ -146,7 +134,7 @@ def clean_mesh(verts, faces, colors=None, min_f=64, min_d=20.0, keep="all"):
         raise ValueError(f"{what}: min_d must be a finite number >= 0 (got {min_d!r})")
     dev = verts.device
     if dev.type != "cuda" or faces.device != dev or (colors is not None and colors.device != dev):
-        raise _no_cpu_path(what)
+        raise _args.no_cpu_path(what)
     V, F = int(verts.shape[0]), int(faces.shape[0])
     min_f, min_d = int(min_f), float(min_d)
     verts = verts.detach().contiguous()
@@ -155,7 +143,7 @@ def clean_mesh(verts, faces, colors=None, min_f=64, min_d=20.0, keep="all"):
     with torch.cuda.device(dev):
         st = _lib.stream(dev)
         if F:
-            _check_range(what, faces, V)
+            _args.check_index_range(what, _args.FACE_INDICES, faces, V)
         faces32 = faces.detach().to(torch.int32).contiguous()
         state = torch.empty(_lib.DM4D_MCL_STATE_WORDS, **i32)
         null_face, alive = torch.empty(F, **u8), torch.empty(F, **u8)
@@ -220,7 +208,7 @@ def main(argv=None):
 
     args = _parser().parse_args(argv)
     if not torch.cuda.is_available():
-        raise _no_cpu_path("mesh_clean")
+        raise _args.no_cpu_path("mesh_clean")
     mesh = wf.read_mesh(args.mesh_path)
     print(f"Input mesh has {len(mesh['verts'])} vertices and {len(mesh['faces'])} triangles")
     dev = torch.device("cuda:0")

@@ -25,6 +25,8 @@ import os
 import numpy as np
 import torch
 
+from . import _args
+
 KEY_BITS = 62
 
 
@@ -60,8 +62,7 @@ def grid_parameters(lo, hi, scale=64, voxel_size=None):
 
 def check_face_range(fmin, fmax, n_verts):
     """Raises ValueError unless every face index lies in [0, n_verts)."""
-    if fmin < 0 or fmax >= n_verts:
-        raise ValueError(f"simplify_vertex_clustering: face indices span [{fmin}, {fmax}], the mesh has {n_verts} vertices")
+    _args.check_span("simplify_vertex_clustering", _args.FACE_INDICES, fmin, fmax, n_verts)
 
 
 def simplify_vertex_clustering(verts, faces, colors=None, scale=64, voxel_size=None):
@@ -76,8 +77,7 @@ def simplify_vertex_clustering(verts, faces, colors=None, scale=64, voxel_size=N
         raise TypeError("simplify_vertex_clustering: verts, faces and colors must be torch tensors")
     if verts.ndim != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32 or verts.shape[0] == 0:
         raise ValueError(f"simplify_vertex_clustering: verts must be float32 [V,3] with V > 0 (got {verts.dtype} {tuple(verts.shape)})")
-    if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"simplify_vertex_clustering: faces must be int32 / int64 [F,3] (got {faces.dtype} {tuple(faces.shape)})")
+    _args.check_face_tensor("simplify_vertex_clustering", faces)
     if colors is not None and (colors.shape != verts.shape or colors.dtype != torch.float32):
         raise ValueError(f"simplify_vertex_clustering: colors must be float32 {tuple(verts.shape)} (got {colors.dtype} {tuple(colors.shape)})")
     if voxel_size is None:
@@ -95,8 +95,7 @@ def simplify_vertex_clustering(verts, faces, colors=None, scale=64, voxel_size=N
         # the only values that visit the host: six bounds, the two extreme face indices, and the counts
         bounds = torch.cat([verts.amin(0), verts.amax(0)]).double().cpu().tolist()
         if F:
-            fmin, fmax = torch.stack([faces.amin(), faces.amax()]).cpu().tolist()
-            check_face_range(fmin, fmax, V)
+            _args.check_index_range("simplify_vertex_clustering", _args.FACE_INDICES, faces, V)
         voxel, origin, dims = grid_parameters(bounds[:3], bounds[3:], scale, voxel_size)
         keys = torch.empty(V, **i64)
         _lib.call("dm4d_simplify_vertex_keys", V, verts.data_ptr(), origin[0], origin[1], origin[2], voxel, dims[0], dims[1], dims[2],

@@ -18,18 +18,12 @@ from collections import namedtuple
 import torch
 
 from . import _lib, knn as _knn
+from ._args import check_index_range as _check_range
 
 K_MAX = _lib.DM4D_SR_MAX_K
 CHUNK = _lib.DM4D_SR_CHUNK
 
 SugarReg = namedtuple("SugarReg", ["density_regulation", "normal_regulation", "density", "beta", "density_term", "normal_term"])
-
-
-def _check_range(what, name, t, n):
-    """Values of the device tensor `t` lie in [0, n): one host read."""
-    lo, hi = (int(v) for v in torch.stack((t.min(), t.max())).cpu())
-    if lo < 0 or hi >= n:
-        raise ValueError(f"{what}: {name} has values in [{lo}, {hi}], outside [0, {n})")
 
 
 def reverse_table(knn_idx):

@@ -52,11 +52,11 @@ def test_expected_rows_is_the_reference_order():
 
 def test_library_exports_the_header():
     L = _lib.lib()
-    names = _lib.dc_declared_symbols()
+    names = _lib.declared_symbols("dc")
     assert {"dm4d_dc_version", "dm4d_dc_accumulate_stats", "dm4d_dc_classify_densify", "dm4d_dc_classify_prune", "dm4d_dc_plan_count",
             "dm4d_dc_plan_rows", "dm4d_dc_move", "dm4d_dc_reset_opacity"} <= set(names)
     assert [n for n in names if not hasattr(L, n)] == []
-    assert L.dm4d_dc_version() == _lib.dc_abi_version() == 1
+    assert L.dm4d_dc_version() == _lib.abi_version("dc") == 1
     assert _lib.abi_version() == 107                    # include/dm4d.h keeps its number
     assert (dc.KEEP, dc.DROP, dc.CLONE, dc.SPLIT) == (0, 1, 2, 3)
 

@@ -103,14 +103,14 @@ def test_vertex_and_face_order_follow_the_rule(random_mesh):
 
 # ------------------------------------------------------------------------------------------------------- header, binding
 def test_new_header_parses_and_the_library_exports_it():
-    names = _lib.iso_declared_symbols()
-    assert names == sorted(_lib._ISO_SIGNATURES) and len(names) == 7 and all(n.startswith("dm4d_iso_") for n in names)
+    names = _lib.declared_symbols("iso")
+    assert names == sorted(_lib._PARSED["iso"][2]) and len(names) == 7 and all(n.startswith("dm4d_iso_") for n in names)
     L = _lib.lib()
     for n in names:
         assert hasattr(L, n), n
-    assert L.dm4d_iso_version() == _lib.iso_abi_version() == _lib._ISO_CONSTANTS["DM4D_ISO_ABI_VERSION"] == 1
+    assert L.dm4d_iso_version() == _lib.abi_version("iso") == _lib._PARSED["iso"][0]["DM4D_ISO_ABI_VERSION"] == 1
     assert len(_lib._SIGNATURES) == 127 and not set(names) & set(_lib._SIGNATURES) and _lib.abi_version() == 107
-    assert _lib._ISO_STRUCTS == {}
+    assert _lib._PARSED["iso"][1] == {}
 
 
 def test_entry_points_validate_before_any_launch():

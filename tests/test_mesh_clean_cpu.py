@@ -81,12 +81,12 @@ def test_blob_field_floaters_fall_under_the_defaults():
 
 def test_library_exports_the_header():
     L = _lib.lib()
-    names = _lib.mcl_declared_symbols()
+    names = _lib.declared_symbols("mcl")
     assert names == ["dm4d_mcl_compact", "dm4d_mcl_component_stats", "dm4d_mcl_components_round", "dm4d_mcl_face_first",
                      "dm4d_mcl_face_flags", "dm4d_mcl_keep", "dm4d_mcl_version"]
     assert [n for n in names if not hasattr(L, n)] == []
-    assert L.dm4d_mcl_version() == _lib.mcl_abi_version() == 1
-    assert _lib.abi_version() == 107 and _lib.dc_abi_version() == 1 and _lib.iso_abi_version() == 1 and _lib.sr_abi_version() == 1
+    assert L.dm4d_mcl_version() == _lib.abi_version("mcl") == 1
+    assert _lib.abi_version() == 107 and _lib.abi_version("dc") == 1 and _lib.abi_version("iso") == 1 and _lib.abi_version("sr") == 1
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.SO_PATH], capture_output=True, text=True, check=True).stdout
     assert sorted(ln.split()[-1] for ln in out.splitlines() if " T dm4d_mcl_" in ln) == names
     assert _lib.DM4D_MCL_STATE_WORDS == 16 and _lib.DM4D_MCL_STATE_BEST % 2 == 0

@@ -47,11 +47,11 @@ def test_torch_expressions_agree_with_the_restatement():
 
 def test_library_exports_the_header():
     L = _lib.lib()
-    names = _lib.sr_declared_symbols()
+    names = _lib.declared_symbols("sr")
     assert names == ["dm4d_sr_backward", "dm4d_sr_forward", "dm4d_sr_scratch_bytes", "dm4d_sr_version"]
     assert [n for n in names if not hasattr(L, n)] == []
-    assert L.dm4d_sr_version() == _lib.sr_abi_version() == 1
-    assert _lib.abi_version() == 107 and _lib.dc_abi_version() == 1 and _lib.iso_abi_version() >= 1     # the others keep their numbers
+    assert L.dm4d_sr_version() == _lib.abi_version("sr") == 1
+    assert _lib.abi_version() == 107 and _lib.abi_version("dc") == 1 and _lib.abi_version("iso") >= 1     # the others keep their numbers
     import subprocess
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.SO_PATH], capture_output=True, text=True, check=True).stdout
     assert sorted(ln.split()[-1] for ln in out.splitlines() if " T dm4d_sr_" in ln) == names
