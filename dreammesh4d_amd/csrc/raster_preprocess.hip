@@ -411,17 +411,24 @@ __device__ __forceinline__ void gather_gaussian(const BatchDesc &d, const ViewCt
     float acc[7 + kMaxChannels];
 #pragma unroll
     for (int k = 0; k < 7 + kMaxChannels; ++k) acc[k] = 0.f;
-    const int r = live ? radii[i] : 0;
     const int C = vp.C;
-    // the per-Gaussian inputs of the preprocess backward are requested BEFORE the records are streamed (round 6: their round trip used to follow
-    // the record sum; k_gather_face_bwd<2> 287.5 -> 277.1 us per 20 views)
+    // ONE round trip before the first record byte: a live lane's radius, record count and first record (all [N] arrays) and the
+    // per-Gaussian inputs of the preprocess backward are requested together and unconditionally; the conditions apply to the loaded
+    // VALUES (the loads used to be chained radii -> rec_touched -> cellinfo, three dependent trips in a wave that streams ~14 KB).
+    // Round 6 had moved the preprocess inputs ahead of the record stream (k_gather_face_bwd<2> 287.5 -> 277.1 us per 20 views).
+    int r = 0;
+    uint32_t cnt = 0u, first = 0u;
     f3 h_m = {0.f, 0.f, 0.f}, h_sc = {0.f, 0.f, 0.f};
     float4 h_q = make_float4(1.f, 0.f, 0.f, 0.f), h_co = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r > 0) {
+    if (live) {
+        r = radii[i];
+        cnt = g.rec_touched[i];
+        first = g.rec0[i];          // == cellinfo[i].z (K3 writes both); garbage where the Gaussian touches no tile: used under cnt > 0 only
         h_m = load3(in.means3D, i);
         if (!in.cov3D_precomp) { h_q = reinterpret_cast<const float4 *>(in.rotations)[i]; h_sc = load3(in.scales, i); }
         h_co = g.conic_opacity[i];
     }
+    if (!(r > 0)) h_co = make_float4(0.f, 0.f, 0.f, 0.f);      // a culled Gaussian's conic is not written
     {
         // The records of a Gaussian are one contiguous block (its reached cells, K1), the blocks of consecutive
         // Gaussians follow each other (K3's scan), and B1 wrote every record -- real sums for the entries the
@@ -431,12 +438,9 @@ __device__ __forceinline__ void gather_gaussian(const BatchDesc &d, const ViewCt
         const bool lean = d.lean != 0;
         constexpr int RS = PARTS * 4;
         uint32_t rec0 = 0xFFFFFFFFu, end = 0u;
-        if (r > 0) {
-            const uint32_t cnt = g.rec_touched[i];
-            if (cnt > 0u) {
-                rec0 = g.cellinfo[i].z;
-                end = min(rec0 + cnt, max(rec0, c.rec_cap));
-            }
+        if (r > 0 && cnt > 0u) {
+            rec0 = first;
+            end = min(rec0 + cnt, max(rec0, c.rec_cap));
         }
         uint32_t R0 = rec0, R1 = end;
         R0 = wave_min_u32(R0);

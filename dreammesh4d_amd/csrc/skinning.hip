@@ -589,28 +589,52 @@ constexpr int kCornerRec = 6;   // dL/dx (3) + dL/d(rotation-vector blend) (3) p
 // dL/dnormal.  vxyz / vrot / rec: the frame's.  Called by every thread of the workgroup (two barriers inside).
 // The Exp / Exp-gradient of a slot is the heavy part and runs G-wide in parallel; the G slot results of a face meet in LDS and
 // the slot-0 thread adds them in slot order (fixed: deterministic) and finishes the face.
+// What face_bwd_finish reads from memory, per thread: the slot's static quaternion and, in the first three slots of a face (G >= 3),
+// the rotation and position of corner `sl` -- one corner per thread, handed on through LDS, where slot 0 used to walk faces -> vxyz for
+// all three after the second barrier.  The corner INDEX is a function of its own so that a caller can request it early (the fused
+// gather + face kernel: before its record stream), which takes the first hop of the chain faces -> vrot / vxyz out of the face part.
+struct FaceOperands { float4 qs; q4 vq; v3 vx; };
+// the corner a thread fetches for its face: vertex `sl` in the first three slots of a face (G >= 3), else none (-1)
+__device__ __forceinline__ int face_bwd_corner(const int G, const int32_t *__restrict__ faces, const bool live, const int f, const int sl)
+{
+    return (live && G >= 3 && sl < 3) ? faces[3 * f + sl] : -1;
+}
+__device__ __forceinline__ FaceOperands face_bwd_operands(const int G, const int vi, const float *__restrict__ vxyz,
+                                                          const float *__restrict__ vrot, const float *__restrict__ q_static,
+                                                          const bool has_rots, const bool has_normals, const bool live, const int f,
+                                                          const int sl)
+{
+    FaceOperands p = {make_float4(0.f, 0.f, 0.f, 0.f), q4{0.f, 0.f, 0.f, 0.f}, mk3(0, 0, 0)};
+    if (!live) return p;
+    if (has_rots) p.qs = reinterpret_cast<const float4 *>(q_static)[(size_t)f * G + sl];
+    if (vi >= 0) {
+        if (has_rots) p.vq = ldq(vrot, vi);
+        if (has_normals) p.vx = ld3(vxyz, vi);
+    }
+    return p;
+}
+
 __device__ __forceinline__ void face_bwd_finish(const int F, const int G, const int32_t *__restrict__ faces,
                                                 const float *__restrict__ vxyz, const float *__restrict__ vrot,
-                                                const float *__restrict__ q_static, const bool has_means, const bool has_rots,
+                                                const FaceOperands &pre, const bool has_means, const bool has_rots,
                                                 const bool has_normals, const bool live, const int f, const int sl, const int base,
                                                 const v3 gm, const q4 go, const v3 gn_in, float *__restrict__ rec, const int pypose,
                                                 float (*s_log)[3] /* LDS [kSkinThreads][3]: per thread of a face's first three slots: Log of vertex (tid % G) */,
-                                                float (*s_val)[9] /* LDS [kSkinThreads][9]: per slot: gm (3), gr (3), gn (3) */)
+                                                float (*s_val)[9] /* LDS [kSkinThreads][9]: per slot: gm (3), gr (3), gn (3) */,
+                                                float (*s_vx)[3] /* LDS [kSkinThreads][3]: like s_log: position of vertex (tid % G) */)
 {
     const int tid = threadIdx.x;
-    // phase A: Log of the three vertex rotations, one per thread (G >= 3) or all by slot 0 (G == 1)
-    if (live && has_rots) {
-        if (G >= 3) {
-            if (sl < 3) {
-                const v3 L = so3_log(ldq(vrot, faces[3 * f + sl]));
-                s_log[base + sl][0] = L.x; s_log[base + sl][1] = L.y; s_log[base + sl][2] = L.z;
-            }
-        }      // G == 1: the single slot computes the three logs itself (below)
-    }
+    // phase A: Log of the three vertex rotations, one per thread (G >= 3) or all by slot 0 (G == 1); the corner positions go the same way
+    if (live && G >= 3 && sl < 3) {
+        if (has_rots) {
+            const v3 L = so3_log(pre.vq);
+            s_log[base + sl][0] = L.x; s_log[base + sl][1] = L.y; s_log[base + sl][2] = L.z;
+        }
+        if (has_normals) { s_vx[base + sl][0] = pre.vx.x; s_vx[base + sl][1] = pre.vx.y; s_vx[base + sl][2] = pre.vx.z; }
+    }      // G == 1: the single slot computes the three logs and loads the three positions itself (below)
     __syncthreads();
     // phase B: per slot
     if (live) {
-        const size_t i = (size_t)f * G + sl;
         const float *b = c_bary[bary_row(G)][sl];
         v3 gr = mk3(0, 0, 0);
         if (has_rots) {
@@ -626,7 +650,7 @@ __device__ __forceinline__ void face_bwd_finish(const int F, const int G, const 
             }
             const v3 r = (b[0] * L0 + b[1] * L1) + b[2] * L2;
             const q4 qd = so3_exp(r);
-            const float4 qs4 = reinterpret_cast<const float4 *>(q_static)[i];
+            const float4 qs4 = pre.qs;
             const q4 qs = q4{qs4.y, qs4.z, qs4.w, qs4.x};
             const q4 Q = qmul(qd, qs);
             const float nq = fmaxf(sqrtf(qdot(Q, Q)), 1e-12f);
@@ -652,8 +676,14 @@ __device__ __forceinline__ void face_bwd_finish(const int F, const int G, const 
         gn = gn + mk3(o[6], o[7], o[8]);
     }
     if (has_normals) {
-        const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-        const v3 x0 = ld3(vxyz, i0), x1 = ld3(vxyz, i1), x2 = ld3(vxyz, i2);
+        v3 x0, x1, x2;
+        if (G >= 3) {
+            x0 = mk3(s_vx[base][0], s_vx[base][1], s_vx[base][2]);
+            x1 = mk3(s_vx[base + 1][0], s_vx[base + 1][1], s_vx[base + 1][2]);
+            x2 = mk3(s_vx[base + 2][0], s_vx[base + 2][1], s_vx[base + 2][2]);
+        } else {
+            x0 = ld3(vxyz, faces[3 * f]); x1 = ld3(vxyz, faces[3 * f + 1]); x2 = ld3(vxyz, faces[3 * f + 2]);
+        }
         const v3 e1 = x1 - x0, e2 = x2 - x0, c = cross(e1, e2);
         const float cn = fmaxf(sqrtf(dot(c, c)), 1e-12f);
         const v3 nn = (1.f / cn) * c;
@@ -717,8 +747,10 @@ __global__ __launch_bounds__(kSkinThreads) void k_face_bwd_face(int F, int G, in
     }
     __shared__ float s_log[kSkinThreads][3];
     __shared__ float s_val[kSkinThreads][9];
-    face_bwd_finish(F, G, faces, vxyz, vrot, q_static, g_means != nullptr, g_rots != nullptr, g_normals != nullptr, live, f, sl, fl * G,
-                    gm, go, gn, rec, pypose, s_log, s_val);
+    __shared__ float s_vx[kSkinThreads][3];
+    const FaceOperands pre = face_bwd_operands(G, face_bwd_corner(G, faces, live, f, sl), vxyz, vrot, q_static, g_rots != nullptr, g_normals != nullptr, live, f, sl);
+    face_bwd_finish(F, G, faces, vxyz, vrot, pre, g_means != nullptr, g_rots != nullptr, g_normals != nullptr, live, f, sl, fl * G,
+                    gm, go, gn, rec, pypose, s_log, s_val, s_vx);
 }
 
 // per vertex: fixed-order sum over incident face corners (static CSR), then Log backward
