@@ -242,6 +242,10 @@ int dm4d_adamw_message(const dm4d_grad_segments *segments, const dm4d_adamw_args
     if (rc) return rc;
     if (!a || !a->exp_avg || !a->exp_avg_sq || !a->step || !a->scratch) { set_error("adamw: null state"); return DM4D_ERR_INVALID; }
     if (a->n_groups < 1 || a->n_groups > 8) { set_error("adamw: %d groups (1..8)", a->n_groups); return DM4D_ERR_INVALID; }
+    if (!(a->beta1 >= 0.f && a->beta1 < 1.f && a->beta2 >= 0.f && a->beta2 < 1.f && a->eps >= 0.f)) {       // (as dm4d_adamw_step: a beta of 1 divides by a zero bias correction)
+        set_error("adamw: betas (%g, %g) / eps %g out of range", a->beta1, a->beta2, a->eps);
+        return DM4D_ERR_INVALID;
+    }
     for (int k = 0; k < d.seg.n_seg; ++k) {
         if (d.seg.count[k] > 0 && !a->param[k]) { set_error("adamw: null parameter storage (segment %d)", k); return DM4D_ERR_INVALID; }
         if (a->group[k] < 0 || a->group[k] >= a->n_groups) { set_error("adamw: segment %d in group %d", k, a->group[k]); return DM4D_ERR_INVALID; }
